@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Benchmark: env-steps/s of GAE + PPO update (one learn()) on synthetic [128 x num_envs] buffers.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lunar8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lunar8192] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--config lunar8192]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W [--config c5]
+        --master-port P bench.py --gpus N --steps K --warmup W [--config c5] [--full]
 
 ``python bench.py --gpus N`` with N > 1 and no launcher around it starts the N ranks itself (one
 child torch.distributed.run job; the parent touches no GPU) and exits with the job's status; a
@@ -24,17 +25,28 @@ STRONG-scaling run: 65,536 envs in total split over the ranks (8,192 per GPU at 
 term ~ Bern(0.02), trunc ~ Bern(0.005), uniform actions, default_rng(rank); random-init weights
 of the reference architecture.
 
-Rank 0 prints ONE JSON line.  ``value`` comes from a timed pass with nothing but the learn()
-work in the stream.  A second timed pass of the same K learns stamps every kernel with its own
+Rank 0 prints ONE JSON line.  ``value`` and ``ms_per_step`` come from a timed pass of K learns
+with nothing but the learn() work in the stream.  A plain run does only that: set up, W warm-up
+learns, the K timed learns, the line.  The weights (torch seed 0), the rollout (default_rng(rank))
+and the NumPy RNG the permutations are drawn from (seed 0) are the same from run to run, and
+``--dump-outputs DIR`` writes what the last timed learn() left its caller as float32
+``DIR/<name>.npy``: ``params`` (the flat parameter buffer), ``adam_exp_avg`` / ``adam_exp_avg_sq``
+(Adam's moments) and ``learn_trace`` ([E*M, 5] loss, policy loss, value loss, entropy, gradient
+norm of that learn's optimizer steps), so two builds compare output for output.
+
+Everything else is measured only with ``--full`` (the ``--no-*`` options trim it).  There a second
+timed pass of the same K learns runs on a rollout whose next_obs never continues into obs
+(``value_unchained_obs``), and a third stamps every kernel with its own
 start/end HIP events (libdppo timing mode): ``kernels``, ``device_ms_per_step`` and ``roofline``
 (the dominant kernel by device time, its average launch duration, algorithmic FLOP per launch)
-come from it, never the throughput.  At N = 1 the line also carries ``configs_extra`` (C2
+come from it, never the throughput.  At N = 1 the full line also carries ``configs_extra`` (C2
 CartPole 4096, C4 HalfCheetah 4096 and C5's 65,536 envs on one GPU -- the strong-scaling
 anchor), ``roofline_gae`` (the GAE kernel at num_envs = 8192 over 16 rotating buffer sets, 368 MB
 > the 256 MB Infinity Cache; ``roofline_gae_affine`` the tolerance-mode kernel, and
 ``roofline_gae_65536`` both at C5's one-GPU 65,536 envs) and ``cpu_baseline``: the PyTorch-CPU
 restatement of the reference path (oracle/ppo_torch.py) timed for one full learn() of the
-headline workload on the host cores, with the NumPy oracle beside it as ``cpu_baseline_numpy``.
+headline workload on the host cores, with the NumPy oracle beside it as ``cpu_baseline_numpy``;
+at N > 1, ``multi_gpu`` (configs[4] strong scaling and the gradient exchange).
 """
 from __future__ import annotations
 
@@ -299,10 +311,23 @@ def cpu_baselines_child(cfg_name):
     return tb, nb
 
 
+def dump_outputs(agent, folder):
+    """What the last learn() left its caller, as float32 ``folder/<name>.npy``: the flat parameter
+    buffer, Adam's two moment buffers and the learn's per-optimizer-step trace."""
+    L = agent._learner
+    os.makedirs(folder, exist_ok=True)
+    arrays = {"params": L.flat.flat, "adam_exp_avg": L.m, "adam_exp_avg_sq": L.v}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays["learn_trace"] = agent.learn_trace()
+    for k, v in arrays.items():
+        np.save(os.path.join(folder, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def run_config(name, world, rank, dist, device, steps, warmup, kernel_timing=True,
-               global_mb=False, keep_agent=False):
+               global_mb=False, keep_agent=False, full=True, dump_dir=None):
     """Time `steps` learn() calls of CONFIGS[name] on this rank; returns the measurement dict
-    (max wall time over ranks)."""
+    (max wall time over ranks).  full=False: the throughput pass alone (no unchained pass, no
+    per-kernel pass).  dump_dir: dump_outputs() there right after the throughput pass."""
     import diamond
     from diamond import _native as NN
     model, T, Nc, D, A, cont, pt, ptr, scaling = CONFIGS[name]
@@ -313,6 +338,9 @@ def run_config(name, world, rank, dist, device, steps, warmup, kernel_timing=Tru
     Agent = diamond.ContinuousPPO if cont else diamond.PPO
     cfg = Cfg(rollout_steps=T, num_envs=N, verbose=False, total_steps=10 ** 12,
               global_minibatches=global_mb)
+    # the same initial weights and the same minibatch permutations in every run
+    torch.manual_seed(0)
+    np.random.seed(0)
     agent = Agent(None, cfg, envs=SpecEnvs(D, A, cont))
     assert agent._learner.fused, "benchmark must exercise the fused HIP path"
     ro, _ = synth_rollout(T, N, D, A, cont, pt, ptr, seed=rank, device=device)
@@ -353,19 +381,23 @@ def run_config(name, world, rank, dist, device, steps, warmup, kernel_timing=Tru
                                                                       "draft_start", "draw",
                                                                       "slot_wait")}
     hits = hs["lookahead_hits"]
+    if dump_dir is not None:
+        dump_outputs(agent, dump_dir)
     # Pass A' (reported beside it): the same learns on a rollout whose next_obs never continues
     # into obs -- the old-policy evaluation's next-value reuse (mlp.hip) then finds nothing to
     # reuse and runs the full critic pass on next_obs
-    ro_chained = ro
-    ro, _ = synth_rollout(T, N, D, A, cont, pt, ptr, seed=rank, device=device, chained=False)
-    agent.learn_device(ro)
-    elapsed_unchained = timed_pass(False)
-    ro = ro_chained
+    elapsed_unchained = None
+    if full:
+        ro_chained = ro
+        ro, _ = synth_rollout(T, N, D, A, cont, pt, ptr, seed=rank, device=device, chained=False)
+        agent.learn_device(ro)
+        elapsed_unchained = timed_pass(False)
+        ro = ro_chained
     # Pass B (the per-kernel table and the roofline): the same K learns with the kernels' own
     # start/end HIP events (libdppo timing mode); never the throughput.
     timing = {k: (0.0, 0) for k in NN.TIMING_CLASSES}
     elapsed_instr = None
-    if kernel_timing:
+    if full and kernel_timing:
         elapsed_instr = timed_pass(True)
         timing = h.timing()
     h.set_timing(False)
@@ -408,7 +440,8 @@ def run_config(name, world, rank, dist, device, steps, warmup, kernel_timing=Tru
         "value": round(B_global * steps / elapsed, 1),
         "ms_per_step": round(elapsed / steps * 1e3, 4),
         "update_steps_per_s": round(E * M * steps / elapsed, 1),
-        "value_unchained_obs": round(B_global * steps / elapsed_unchained, 1),
+        "value_unchained_obs": (round(B_global * steps / elapsed_unchained, 1)
+                                if elapsed_unchained else None),
         "scaling": scaling,
         "config": {"workload": f"{model}: learn() = old-policy eval + GAE + adv-norm + "
                                f"{E}x{M} minibatch Adam steps", "name": name,
@@ -440,6 +473,10 @@ def run_config(name, world, rank, dist, device, steps, warmup, kernel_timing=Tru
         "perm_lookahead_hits": hits,
         "final_loss": float(loss_trace[-1, 0]),
     }
+    if not full:  # what only the passes above measure
+        for k in ("value_unchained_obs", "roofline", "kernels", "device_ms_per_step",
+                  "instrumented_ms_per_step"):
+            del res[k]
     if keep_agent:
         res["_agent"] = agent
     del agent, ro
@@ -565,8 +602,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one GPU each); without a torch.distributed launcher, N > 1 "
                          "starts the N ranks itself")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed learn() calls")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed learn() calls before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed learn() computed (parameters, Adam moments, "
+                         "loss trace) as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the unchained-obs and per-kernel passes with the "
+                         "roofline, the CPU baselines, the other configs and the GAE rooflines "
+                         "(N = 1) or the multi-GPU legs (N > 1); the --no-* options trim it")
     ap.add_argument("--config", default="lunar8192", choices=sorted(CONFIGS),
                     help="default: BASELINE configs[2], LunarLander N = 8192 per GPU -- the "
                          "largest single-GPU config (the north star's GAE size)")
@@ -598,7 +642,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    full = args.full
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # first, before this process touches the GPU: the CPU path on the headline workload
         # itself (c5's 65,536 envs: its 4,096-env shape)
         baseline = cpu_baselines_child(args.config if args.config != "c5" else "cartpole4096")
@@ -622,7 +667,8 @@ def main():
 
     main_res = run_config(args.config, world, rank, dist, device, args.steps, args.warmup,
                           kernel_timing=not args.no_kernel_timing,
-                          global_mb=args.global_minibatches)
+                          global_mb=args.global_minibatches, full=full,
+                          dump_dir=args.dump_outputs if rank == 0 else None)
     out = None
     if rank == 0:
         out = {
@@ -639,18 +685,19 @@ def main():
             "dtype": "f32",
             "data": "synthetic",
             "data_note": "random observations/rewards/dones in the reference rollout's layout: "
-                         "obs[t+1] is next_obs[t] unless that env was reset (ppo.py:163-179); "
-                         "value_unchained_obs: the same learns with independent next_obs",
+                         "obs[t+1] is next_obs[t] unless that env was reset (ppo.py:163-179)"
+                         + ("; value_unchained_obs: the same learns with independent next_obs"
+                            if full else ""),
         }
         out.update({k: v for k, v in main_res.items() if k not in out})
         out["device"] = {"name": torch.cuda.get_device_name(device),
                          "arch": getattr(torch.cuda.get_device_properties(device), "gcnArchName", ""),
                          "compute_units": torch.cuda.get_device_properties(device).multi_processor_count}
-    if world > 1 and not args.no_extra:
+    if full and world > 1 and not args.no_extra:
         mg = multi_gpu_report(world, rank, dist, device, min(args.steps, 10), 2)
         if rank == 0:
             out["multi_gpu"] = mg
-    if world == 1 and not args.no_extra:
+    if full and world == 1 and not args.no_extra:
         # the other BASELINE configs on this GPU (C3, C4), and C5's 65,536 global envs on ONE
         # GPU: the anchor of the configs[4] strong-scaling curve (`--config c5 --gpus N`)
         extra = {}
@@ -675,7 +722,7 @@ def main():
         out["headline"] = {"name": args.config, "baseline_config": BASELINE_INDEX.get(args.config),
                            "since": "round 4 (rounds 1-3: configs[1] cartpole4096)",
                            "configs1_cartpole4096_value": c1}
-    if rank == 0 and world == 1 and not args.no_gae_roofline:
+    if full and rank == 0 and world == 1 and not args.no_gae_roofline:
         out["roofline_gae"] = gae_roofline(device)
         out["roofline_gae_affine"] = gae_roofline(device, mode=1)
         # C5's one-GPU buffer (65,536 envs, 184 MB per launch): the launch ramp amortised

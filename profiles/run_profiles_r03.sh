@@ -16,7 +16,7 @@ CONFIGS=${CONFIGS:-cartpole4096 lunar8192 cheetah4096 c5}
 for C in $CONFIGS; do
   D=$OUT/$C
   mkdir -p $D
-  B="$R/bench.py --no-cpu-baseline --no-gae-roofline --no-extra --config $C"
+  B="$R/bench.py --full --no-cpu-baseline --no-gae-roofline --no-extra --config $C"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt -o kt -- \
     python3 $B --steps 6 --warmup 2 > $D/kt.log 2>&1 || exit 1
   timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \

@@ -183,8 +183,8 @@ def test_bench_two_rank_rehearsal_line():
     import sys
     d = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                      "--nproc-per-node=2", "--master-addr=127.0.0.1",
-                     f"--master-port={_free_port()}", "bench.py", "--gpus", "2", "--steps", "3",
-                     "--warmup", "1", "--config", "cartpole4096"])
+                     f"--master-port={_free_port()}", "bench.py", "--full", "--gpus", "2",
+                     "--steps", "3", "--warmup", "1", "--config", "cartpole4096"])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0
     assert d["config"]["exchange"] == "peer" and d["config"]["num_envs_total"] == 2 * 4096
     assert d["kernels"]["allreduce"]["launches"] > 0
@@ -196,7 +196,8 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     sweep): bench.py starts the two ranks itself and rank 0's line says n_gpus 2, on the default
     headline workload (LunarLander, 8192 envs per rank)."""
     import sys
-    d = _bench_line([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"])
+    d = _bench_line([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2",
+                     "--warmup", "1"])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["value"] > 0
     assert d["config"]["name"] == "lunar8192" and d["config"]["num_envs_total"] == 2 * 8192
     assert d["config"]["exchange"] == "peer"
@@ -221,10 +222,44 @@ def test_bench_one_gpu_line_names_its_baseline_config():
     """The N = 1 line (the driver's BENCH line) names which BASELINE config its headline is --
     configs[2] since round 4 -- and carries the roofline of its dominant kernel."""
     import sys
-    d = _bench_line([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-extra",
-                     "--no-cpu-baseline", "--no-gae-roofline"])
+    d = _bench_line([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1",
+                     "--no-extra", "--no-cpu-baseline", "--no-gae-roofline"])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["unit"] == "env-steps/s"
     assert d["config"]["baseline_config"] == "configs[2]"
     assert d["headline"]["name"] == "lunar8192" and d["headline"]["baseline_config"] == "configs[2]"
     r = d["roofline"]
     assert r["bound"] == "mfma" and 0 < r["frac"] < 1 and r["unit"] == "TFLOP/s"
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain ``bench.py --gpus 1 --steps K --warmup W`` times its K learns and nothing else (no
+    per-kernel pass, other configs, rooflines or CPU baselines: those are ``--full``'s), and
+    ``--dump-outputs`` writes the same float32 arrays whenever the arguments are the same: the
+    inputs are seeded and the fused learn() is deterministic.  The second run of the same workload
+    is made in this process (bench.run_config), which spares a second interpreter start."""
+    import sys
+    import torch
+    import bench
+    d = _bench_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                     "--config", "cartpole4096", "--dump-outputs", str(tmp_path / "cli")])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    # value is the env-steps of a timed learn over the time ms_per_step says it took
+    assert d["value"] == pytest.approx(128 * 4096 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("kernels", "roofline", "configs_extra", "roofline_gae", "cpu_baseline",
+              "value_unchained_obs", "multi_gpu"):
+        assert k not in d, k
+    r = bench.run_config("cartpole4096", 1, 0, None, torch.device("cuda", 0), 2, 1, full=False,
+                         dump_dir=str(tmp_path / "here"))
+    assert r["final_loss"] == d["final_loss"]
+    dumps = [{p.name: np.load(p) for p in sorted((tmp_path / w).iterdir())} for w in ("cli", "here")]
+    assert sorted(dumps[0]) == ["adam_exp_avg.npy", "adam_exp_avg_sq.npy", "learn_trace.npy",
+                                "params.npy"]
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+        np.testing.assert_array_equal(a, dumps[1][name], err_msg=name)
+    assert dumps[0]["learn_trace.npy"].shape == (32, 5)
+    assert dumps[0]["learn_trace.npy"][-1, 0] == np.float32(d["final_loss"])
+    assert np.abs(dumps[0]["adam_exp_avg_sq.npy"]).max() > 0   # the learns did step Adam

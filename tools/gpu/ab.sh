@@ -15,6 +15,6 @@ done
 lib() { [ "$1" = main ] && echo diamond-ppo_amd/diamond/libdppo.so || echo diamond-ppo_amd/ab/libdppo_$1.so; }
 for r in $(seq 1 $REPS); do for C in $CS; do for L in main $V; do
   st=20; [ $C = c5 ] && st=8
-  DPPO_LIB=$(lib $L) timeout -k 10 300 python bench.py --config $C --no-extra --no-cpu-baseline --no-gae-roofline --steps $st > $O/$C.$L.$r.json 2>$O/$C.$L.$r.err || { tail -5 $O/$C.$L.$r.err; exit 1; }
+  DPPO_LIB=$(lib $L) timeout -k 10 300 python bench.py --full --config $C --no-extra --no-cpu-baseline --no-gae-roofline --steps $st > $O/$C.$L.$r.json 2>$O/$C.$L.$r.err || { tail -5 $O/$C.$L.$r.err; exit 1; }
   python3 -c "import json;d=json.loads(open('$O/$C.$L.$r.json').read().strip().splitlines()[-1]);k=d['kernels'];print('$C $L rep$r', round(d['value']/1e6,2), d['ms_per_step'], 'radam', k['reduce_adam']['us_avg'], 'grad', k['grad']['us_avg'], 'frac', d['roofline']['frac'])"
 done; done; done

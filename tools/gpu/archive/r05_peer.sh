@@ -9,6 +9,6 @@ for r in 1 2; do for mem in coarse fine uncached; do for w in 2 4; do
   echo "mem=$mem $(tail -1 $O/latency.txt)"
 done; done; done
 for g in 2 8; do
-  DPPO_BENCH_REHEARSE=1 timeout -k 10 600 python bench.py --gpus $g --steps 3 --warmup 1 > $O/rehearse$g.json 2> $O/rehearse$g.err || { echo "rehearse $g failed"; tail -20 $O/rehearse$g.err; exit 1; }
+  DPPO_BENCH_REHEARSE=1 timeout -k 10 600 python bench.py --full --gpus $g --steps 3 --warmup 1 > $O/rehearse$g.json 2> $O/rehearse$g.err || { echo "rehearse $g failed"; tail -20 $O/rehearse$g.err; exit 1; }
   python -c "import json;d=json.loads(open('$O/rehearse$g.json').read().strip().splitlines()[-1]);print($g, json.dumps(d['multi_gpu']))"
 done

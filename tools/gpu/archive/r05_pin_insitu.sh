@@ -4,7 +4,7 @@
 set -o pipefail
 O=gpurun_out/pin2; mkdir -p $O
 for r in 1 2; do for P in 0 1 2; do
-  DPPO_PERM_PAR_PIN=$P timeout -k 10 300 python bench.py --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 8 --warmup 2 > $O/c5_p$P.$r.json 2> $O/c5_p$P.$r.err || exit 1
+  DPPO_PERM_PAR_PIN=$P timeout -k 10 300 python bench.py --full --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 8 --warmup 2 > $O/c5_p$P.$r.json 2> $O/c5_p$P.$r.err || exit 1
   python3 -c "import json;d=json.loads(open('$O/c5_p$P.$r.json').read().strip().splitlines()[-1]);print('pin=$P rep$r C5', round(d['value']/1e6,1), d['ms_per_step'], 'host', d['host_ms_per_step'])"
 done; done
 for P in 0 1 2; do

@@ -1,5 +1,5 @@
 # A/B of an environment switch on one box: $1 = VAR=value, $2 = bench config
-B="python bench.py --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 --warmup 5 --config $2"
+B="python bench.py --full --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 --warmup 5 --config $2"
 for e in "A=0" "$1" "A=0" "$1"; do
   env $e timeout -k 10 200 $B > gpurun_out/eab.json 2>/dev/null || exit 1
   python -c "

@@ -1,4 +1,4 @@
-B="python bench.py --no-extra --no-cpu-baseline --no-gae-roofline --no-kernel-timing --steps 40 --warmup 5"
+B="python bench.py --full --no-extra --no-cpu-baseline --no-gae-roofline --no-kernel-timing --steps 40 --warmup 5"
 run() {
   E="$1"; X="$2 $3"
   timeout -k 10 200 env $E $B $X > gpurun_out/hab.json 2>/dev/null || exit 1

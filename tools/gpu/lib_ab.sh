@@ -5,19 +5,19 @@
 set -o pipefail
 LIBS=$1; REPS=${2:-2}; CFG=${3:-cartpole4096}
 R=$(pwd)
-mkdir -p gpurun_out/lib_ab
+mkdir -p bench_out/lib_ab
 libpath() { [ "$1" = main ] && echo "$R/diamond-ppo_amd/diamond/libdppo.so" || echo "$R/diamond-ppo_amd/build/libdppo_$1.so"; }
 for r in $(seq $REPS); do
   for L in $LIBS; do
-    DPPO_LIB=$(libpath $L) timeout -k 10 200 python bench.py --config $CFG --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 > gpurun_out/lib_ab/$L.json 2>/dev/null || exit 1
-    python3 -c "import json;d=json.loads(open('gpurun_out/lib_ab/$L.json').read().strip().splitlines()[-1]);k=d['kernels'];print('$L', d['value'], d['ms_per_step'], 'dev', d['device_ms_per_step'], 'grad', k['grad']['us_avg'], 'eval', k['eval']['us_avg'], 'radam', k.get('reduce_adam',{}).get('us_avg'))"
+    DPPO_LIB=$(libpath $L) timeout -k 10 200 python bench.py --full --config $CFG --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 > bench_out/lib_ab/$L.json 2>/dev/null || exit 1
+    python3 -c "import json;d=json.loads(open('bench_out/lib_ab/$L.json').read().strip().splitlines()[-1]);k=d['kernels'];print('$L', d['value'], d['ms_per_step'], 'dev', d['device_ms_per_step'], 'grad', k['grad']['us_avg'], 'eval', k['eval']['us_avg'], 'radam', k.get('reduce_adam',{}).get('us_avg'))"
   done
 done
 cd /tmp && export TMPDIR=/tmp
 for L in $LIBS; do
-  D=$R/gpurun_out/lib_ab/pmc_$L
+  D=$R/bench_out/lib_ab/pmc_$L
   DPPO_LIB=$(libpath $L) timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS \
-    --output-format csv -d $D -o p -- python3 $R/bench.py --config $CFG --no-extra --no-cpu-baseline --no-gae-roofline --steps 2 --warmup 1 > $D.log 2>&1 || exit 1
+    --output-format csv -d $D -o p -- python3 $R/bench.py --full --config $CFG --no-extra --no-cpu-baseline --no-gae-roofline --steps 2 --warmup 1 > $D.log 2>&1 || exit 1
   python3 - "$D" "$L" <<'PY'
 import csv, glob, re, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)[0]

@@ -12,14 +12,14 @@ lib() { [ "$1" = main ] && echo diamond-ppo_amd/diamond/libdppo.so || echo diamo
 for C in cheetah4096 lunar8192 cartpole4096; do
   for r in 1 2; do
     for L in r04base main; do
-      DPPO_LIB=$(lib $L) timeout -k 10 200 python bench.py --config $C --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 > $O/$C.$L.json 2>/dev/null || exit 1
+      DPPO_LIB=$(lib $L) timeout -k 10 200 python bench.py --full --config $C --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 > $O/$C.$L.json 2>/dev/null || exit 1
       python3 -c "import json;d=json.loads(open('$O/$C.$L.json').read().strip().splitlines()[-1]);k=d['kernels'];print('$C $L', d['value'], d['ms_per_step'], 'dev', d['device_ms_per_step'], 'grad', k['grad']['us_avg'], 'radam', k['reduce_adam']['us_avg'], d['roofline']['frac'])"
     done
   done
 done
 for C in cartpole4096 lunar8192; do
   for L in main halfslab; do
-    DPPO_LIB=$(lib $L) timeout -k 10 200 python bench.py --config $C --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 > $O/hs.$C.$L.json 2>/dev/null || exit 1
+    DPPO_LIB=$(lib $L) timeout -k 10 200 python bench.py --full --config $C --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 > $O/hs.$C.$L.json 2>/dev/null || exit 1
     python3 -c "import json;d=json.loads(open('$O/hs.$C.$L.json').read().strip().splitlines()[-1]);k=d['kernels'];print('halfslab-ablation $C $L', d['value'], 'grad', k['grad']['us_avg'], 'radam', k['reduce_adam']['us_avg'])"
   done
 done

@@ -30,7 +30,7 @@ print('GAE $L N=65536 LDS bank conflict / LDS active = %.1f%%' % (100*d['SQ_LDS_
 done
 # device resolution at C5 one GPU: value walk (default) vs links+solve, each all-epochs / epoch-wise
 for rep in 1 2; do for cfg in "1 0" "0 0" "1 1" "0 1"; do set -- $cfg
-  DPPO_PERM_WALK=$1 DPPO_PERM_EPOCHWISE=$2 timeout -k 10 300 python bench.py --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 6 --warmup 2 > $O/c5_w$1e$2.$rep.json 2> $O/c5_w$1e$2.$rep.err || exit 1
+  DPPO_PERM_WALK=$1 DPPO_PERM_EPOCHWISE=$2 timeout -k 10 300 python bench.py --full --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 6 --warmup 2 > $O/c5_w$1e$2.$rep.json 2> $O/c5_w$1e$2.$rep.err || exit 1
   python3 -c "import json;d=json.loads(open('$O/c5_w$1e$2.$rep.json').read().strip().splitlines()[-1]);k=d['kernels'];print('C5 walk=$1 epochwise=$2 rep$rep', round(d['value']/1e6,1), 'M/s', d['ms_per_step'], 'ms dev', d['device_ms_per_step'], 'perm', k['perm']['us_avg'], 'us draw', d['host_ms_per_step']['draw'])"
 done; done
 timeout -k 10 400 python tools/gmb_cap.py --out $O/gmb_cap.json > $O/gmb_cap.log 2>&1; echo gmb rc $?; tail -1 $O/gmb_cap.log | cut -c1-2500

@@ -10,7 +10,7 @@ DPPO_PERM_CSR2=1 DPPO_PERM_WALK=$W timeout -k 10 600 python -u -m pytest tests/t
 rc=$?; echo "walk=$W: $(tail -1 $O/pytest_w$W.log)"; [ $rc -eq 0 ] || exit $rc
 done
 for r in 1 2; do for M in 1 0; do
-  DPPO_PERM_CSR2=$M timeout -k 10 300 python bench.py --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 8 > $O/c5.$M.$r.json 2>$O/c5.$M.$r.err || { tail -5 $O/c5.$M.$r.err; exit 1; }
+  DPPO_PERM_CSR2=$M timeout -k 10 300 python bench.py --full --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 8 > $O/c5.$M.$r.json 2>$O/c5.$M.$r.err || { tail -5 $O/c5.$M.$r.err; exit 1; }
   python3 -c "import json;d=json.loads(open('$O/c5.$M.$r.json').read().strip().splitlines()[-1]);k=d['kernels'];print('c5 csr2=$M rep$r', round(d['value']/1e6,2), d['ms_per_step'], {c: round(v['ms_total']/v['launches'],3) for c, v in k.items() if c in ('perm','grad','eval')})"
 done; done
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

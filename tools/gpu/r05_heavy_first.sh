@@ -8,6 +8,6 @@ python3 -c "
 import json; d=json.load(open('$O/gmb_cap.json'))
 for r in d['rows']: print(r['world'], 'serial', r['host_draw_ms_serial'], 'par', r['host_draw_ms_parallel'], 'chained', r['host_draw_ms_parallel_chained'], 'dev', r.get('device_ms_per_learn_global'), 'cap iso', r.get('speedup_cap_parallel_draw'), 'cap chained', r.get('speedup_cap_parallel_chained_draw'))"
 for r in 1 2; do
-timeout -k 10 300 python bench.py --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 8 --warmup 2 > $O/c5.$r.json 2> $O/c5.$r.err || exit 1
+timeout -k 10 300 python bench.py --full --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --steps 8 --warmup 2 > $O/c5.$r.json 2> $O/c5.$r.err || exit 1
 python3 -c "import json;d=json.loads(open('$O/c5.$r.json').read().strip().splitlines()[-1]);print('C5', round(d['value']/1e6,1), d['ms_per_step'], d['host_ms_per_step'])"
 done

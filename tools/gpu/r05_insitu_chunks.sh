@@ -1,7 +1,7 @@
 # Per-chunk timings of the parallel draw inside the C5 one-GPU learn (DPPO_PAR_DBG_CHUNKS=1).
 set -o pipefail
 O=gpurun_out/insitu; mkdir -p $O
-DPPO_PAR_DBG_CHUNKS=1 timeout -k 10 300 python bench.py --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --no-kernel-timing --steps 8 --warmup 2 > $O/c5.json 2> $O/c5.err || { tail -5 $O/c5.err; exit 1; }
+DPPO_PAR_DBG_CHUNKS=1 timeout -k 10 300 python bench.py --full --config c5 --no-extra --no-cpu-baseline --no-gae-roofline --no-kernel-timing --steps 8 --warmup 2 > $O/c5.json 2> $O/c5.err || { tail -5 $O/c5.err; exit 1; }
 python3 - <<'PY'
 import re, json
 lines = [l for l in open('gpurun_out/insitu/c5.err') if l.startswith('chunk')]

@@ -14,6 +14,6 @@ import csv
 rows=list(csv.DictReader(open('$f')))
 g=[x for x in rows if 'gae_pipe' in x['Name']][0]
 print('cold NT=$V rep$rep: gae avg %.2f us min %.2f' % (float(g['AverageNs'])/1e3, float(g['MinNs'])/1e3))"
-  DPPO_GAE_NT=$V timeout -k 10 300 python bench.py --config lunar8192 --no-extra --no-cpu-baseline --steps 20 --warmup 3 > $O/l_${V}_$rep.json 2>/dev/null || exit 1
+  DPPO_GAE_NT=$V timeout -k 10 300 python bench.py --full --config lunar8192 --no-extra --no-cpu-baseline --steps 20 --warmup 3 > $O/l_${V}_$rep.json 2>/dev/null || exit 1
   python3 -c "import json;d=json.loads(open('$O/l_${V}_$rep.json').read().strip().splitlines()[-1]);k=d['kernels'];g=d['roofline_gae'];print('learn NT=$V rep$rep', round(d['value']/1e6,2), d['ms_per_step'], 'gae', k['gae']['us_avg'], 'pack', k['pack']['us_avg'], 'roofline_gae us', g.get('us_per_launch', g.get('kernel_us')), 'ceiling', g.get('ceiling_us'), 'frac_ceil', g.get('frac_of_ceiling'))"
 done; done

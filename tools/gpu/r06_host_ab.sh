@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/r06host; mkdir -p $O
 run() {
   local tag=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --config lunar8192 --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 --warmup 5 > $O/$tag.json 2>/dev/null || return 1
+  env "$@" timeout -k 10 300 python bench.py --full --config lunar8192 --no-extra --no-cpu-baseline --no-gae-roofline --steps 20 --warmup 5 > $O/$tag.json 2>/dev/null || return 1
   python3 -c "import json;d=json.loads(open('$O/$tag.json').read().strip().splitlines()[-1]);h=d['host_ms_per_step'];print('$tag', round(d['value']/1e6,2), d['ms_per_step'], 'dev', d['device_ms_per_step'], 'perms', h['perms'], 'draw', h['draw'], 'slot', h['slot_wait'], 'enq', h['enqueue'], d['host_placement'])"
 }
 nproc; cat /proc/loadavg

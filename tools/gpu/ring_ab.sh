@@ -1,5 +1,5 @@
 # A/B of the MT19937 producer ring (DPPO_PERM_RING) in bench.py, C2 and C3
-B="python bench.py --no-extra --no-cpu-baseline --no-gae-roofline --no-kernel-timing --steps 30 --warmup 5"
+B="python bench.py --full --no-extra --no-cpu-baseline --no-gae-roofline --no-kernel-timing --steps 30 --warmup 5"
 for c in cartpole4096 lunar8192; do
   for r in 1 0 1 0; do
     DPPO_PERM_RING=$r timeout -k 10 200 $B --config $c > gpurun_out/rab.json 2>/dev/null || exit 1
