@@ -87,7 +87,8 @@ struct dppo_handle {
   dppo_layout layout{};
   ParamOffsets po{};
   MlpShape sh{};
-  bool mlp_ok = false;
+  bool mlp_ok = false;  // a fused kernel family applies: tuned or wide
+  bool wide = false;    // ... the wide one (mbwide.hip)
   int64_t B = 0;   // local samples T*N
   int32_t mb = 0;  // local minibatch size B / M
   // global-minibatch data parallelism (dims.global_minibatches with world_size > 1): the host
@@ -379,7 +380,21 @@ struct Timed {
 
 int require_mlp(const dppo_handle* h) {
   if (!h->mlp_ok) {
-    set_error("fused MLP kernels support hidden=64, obs_dim<=32, act_dim<=16 (got H=%d D=%d A=%d)",
+    set_error("fused MLP kernels support act_dim<=16 with hidden=64, obs_dim<=32 (tuned) or, on "
+              "one rank, hidden=128, obs_dim<=128 / hidden=64, 32<obs_dim<=128 (wide) "
+              "(got H=%d D=%d A=%d world=%d)",
+              h->dims.hidden, h->dims.obs_dim, h->dims.act_dim, h->dims.world_size);
+    return DPPO_EUNSUPPORTED;
+  }
+  return DPPO_OK;
+}
+
+// Rollout sampling (act kernels) exists for the tuned class only.
+int require_tuned(const dppo_handle* h) {
+  DPPO_TRY(require_mlp(h));
+  if (h->wide) {
+    set_error("the fused actor kernels support hidden=64, obs_dim<=32, act_dim<=16 only "
+              "(got H=%d D=%d A=%d): sample wide shapes with the network itself",
               h->dims.hidden, h->dims.obs_dim, h->dims.act_dim);
     return DPPO_EUNSUPPORTED;
   }
@@ -497,8 +512,9 @@ int prepare(dppo_handle* h, const dppo_rollout* ro, const float* params, const d
   // (2) old-policy evaluation (ppo.py:235-238)
   {
     Timed tm(h, K_EVAL, s);
-    DPPO_TRY(launch_eval(h->sh, h->po, params, ro->obs, ro->actions, ro->next_obs, h->logp,
-                         h->values, h->next_values, h->B, s, h->reuse_on ? &h->reuse : nullptr));
+    DPPO_TRY(launch_fused_eval(h->sh, h->po, params, ro->obs, ro->actions, ro->next_obs, h->logp,
+                               h->values, h->next_values, h->B, s,
+                               h->reuse_on ? &h->reuse : nullptr));
   }
   // (3) GAE + returns (ppo.py:240-241)
   {
@@ -519,7 +535,7 @@ int prepare(dppo_handle* h, const dppo_rollout* ro, const float* params, const d
   // or unaligned buffers: one partial per 16 envs, 4,096 at N = 65,536) would be ~128 MB of
   // redundant L2 reads per learn -- there the separate reduction launch is cheaper.
   const bool fold_stats =
-      hp->advantage_norm && !distributed(h) && !stats_launch && h->n_partials <= 512;
+      hp->advantage_norm && !distributed(h) && !stats_launch && h->n_partials <= 512 && !h->wide;
   if (hp->advantage_norm && !fold_stats) {
     {
       Timed tm(h, K_STATS, s);
@@ -550,7 +566,16 @@ int prepare(dppo_handle* h, const dppo_rollout* ro, const float* params, const d
   pa.A = d.act_dim;
   pa.R = h->sh.R;
   pa.continuous = d.continuous;
-  {
+  if (h->wide) {
+    // pack_kernel's LDS tile outgrows a CU past D = 32: the wide class packs straight from global
+    // memory, with the statistics finalised by a launch of their own (the same operations)
+    if (hp->advantage_norm) {
+      Timed tm(h, K_STATS, s);
+      DPPO_TRY(launch_stats_finalize(h->dsum, pa.n_total, h->mean_std, s));
+    }
+    Timed tm(h, K_PACK, s);
+    DPPO_TRY(launch_wide_pack(pa, h->mean_std, s));
+  } else {
     Timed tm(h, K_PACK, s);
     DPPO_TRY(launch_pack(pa, s));
   }
@@ -590,11 +615,11 @@ int minibatch_grad(dppo_handle* h, const float* params, const int32_t* idx, cons
   ga.p_total = h->layout.total;
   // with `seg` the size is known only on the device: the handle's grid (sized for the largest
   // share a rank can hold) -- workgroups past the last step contribute zero slabs
-  int G = seg ? h->G : mb_grid(h->sh, m);
+  int G = seg ? h->G : fused_mb_grid(h->sh, m);
   if (G > h->G) G = h->G;
   {
     Timed tm(h, K_GRAD, s);
-    DPPO_TRY(launch_mb(h->sh, h->po, ga, G, s));
+    DPPO_TRY(launch_fused_mb(h->sh, h->po, ga, G, s));
   }
   {
     Timed tm(h, K_REDUCE, s);
@@ -761,10 +786,10 @@ int learn_impl(dppo_handle* h, const dppo_rollout* rollout, float* params, float
         ga.slabs = h->slabs;
         ga.slab_stride = h->slab_stride;
         ga.p_total = h->layout.total;
-        const bool fused_tail = std::getenv("DPPO_FUSED_ADAM") != nullptr && !peer;
+        const bool fused_tail = std::getenv("DPPO_FUSED_ADAM") != nullptr && !peer && !h->wide;
         // with `seg` (global minibatches) the share is known only on the device: the handle's
         // grid, as minibatch_grad
-        int G = seg ? h->G : mb_grid(h->sh, mb, fused_tail);
+        int G = seg ? h->G : fused_mb_grid(h->sh, mb, fused_tail);
         if (G > h->G) G = h->G;
         // DPPO_FUSED_ADAM=1: the slab reduction, clip and Adam as the minibatch kernel's own
         // tail (one launch per minibatch, two grid fan-ins).  Measured: the tail costs what
@@ -793,12 +818,12 @@ int learn_impl(dppo_handle* h, const dppo_rollout* rollout, float* params, float
           fa.ls_n = d.continuous ? d.act_dim : 0;
           fa.add_entropy_const = d.continuous ? 1 : 0;
           Timed tm(h, K_GRAD, s);
-          DPPO_TRY(launch_mb(h->sh, h->po, ga, G, s, &fa));
+          DPPO_TRY(launch_fused_mb(h->sh, h->po, ga, G, s, &fa));
           continue;
         }
         {
           Timed tm(h, K_GRAD, s);
-          DPPO_TRY(launch_mb(h->sh, h->po, ga, G, s));
+          DPPO_TRY(launch_fused_mb(h->sh, h->po, ga, G, s));
         }
         Timed tm(h, K_RADAM, s);
 #ifdef DPPO_ABL_RADAM_G1
@@ -893,9 +918,13 @@ int dppo_create(int device, const dppo_dims* dims, dppo_handle** out) {
   h->sh.A = dims->act_dim;
   h->sh.continuous = dims->continuous;
   h->sh.R = D8 + 4 + (dims->continuous ? (dims->act_dim + 3) / 4 * 4 : 0);
-  h->mlp_ok = dims->hidden == 64 && dims->obs_dim <= 32 && dims->act_dim <= 16 &&
-              mb_lds_bytes(h->sh) <= 160 * 1024 &&
-              (size_t)(h->layout.total + 8) * 4 <= 160 * 1024;
+  h->sh.H = dims->hidden;
+  // tuned class (hidden 64, D <= 32): the minibatch kernels build a slab image in LDS; wide class
+  // (mbwide.hip): single rank only -- multi-rank wide learns stay with the caller's generic path
+  h->wide = !tuned_shape(h->sh) && wide_shape(h->sh) && dims->world_size == 1 &&
+            wide_lds_bytes(h->sh) <= 160 * 1024;
+  h->mlp_ok = h->wide || (tuned_shape(h->sh) && mb_lds_bytes(h->sh) <= 160 * 1024 &&
+                          (size_t)(h->layout.total + 8) * 4 <= 160 * 1024);
   // One fused-minibatch workgroup per CU (its LDS footprint admits exactly one): never launch
   // more workgroups than CUs, or the surplus runs as a second, serialised round.
   int cus = 0;
@@ -903,12 +932,13 @@ int dppo_create(int device, const dppo_dims* dims, dppo_handle** out) {
       cus <= 0)
     cus = 256;
   h->num_cus = cus;
+  h->sh.cus = cus;
   // global minibatches: a rank's share of one varies around mb; size the grid for a whole one
   // (the larger of the two kernels' grids: DPPO_FUSED_ADAM runs the two-team kernel)
   {
     const int32_t mg = h->gmb ? (int32_t)std::min<int64_t>(h->Bg / dims->num_minibatches, h->B)
                               : (h->mb > 0 ? h->mb : 1);
-    h->G = std::max(mb_grid(h->sh, mg), mb_grid(h->sh, mg, true));
+    h->G = std::max(fused_mb_grid(h->sh, mg), fused_mb_grid(h->sh, mg, true));
   }
   if (h->G > cus) h->G = cus;
   h->slab_stride = round_up(h->layout.total + 8, 64);
@@ -1158,8 +1188,8 @@ int dppo_old_policy_f32(dppo_handle* h, const float* params, const float* obs, c
   DPPO_TRY(require_mlp(h));
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   Timed tm(h, K_EVAL, S(stream));
-  return launch_eval(h->sh, h->po, params, obs, actions, next_obs, log_probs, values,
-                     next_values, n, S(stream));
+  return launch_fused_eval(h->sh, h->po, params, obs, actions, next_obs, log_probs, values,
+                           next_values, n, S(stream));
 }
 
 int dppo_act_f32(dppo_handle* h, const float* params, const float* obs, int64_t n, uint64_t seed,
@@ -1168,7 +1198,7 @@ int dppo_act_f32(dppo_handle* h, const float* params, const float* obs, int64_t 
     set_error("invalid argument to dppo_act_f32");
     return DPPO_EINVAL;
   }
-  DPPO_TRY(require_mlp(h));
+  DPPO_TRY(require_tuned(h));
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   return launch_act(h->sh, h->po, params, obs, actions, n, seed, counter, S(stream));
 }
@@ -1180,7 +1210,7 @@ int dppo_act_squash_f32(dppo_handle* h, const float* params, const float* obs, i
     set_error("invalid argument to dppo_act_squash_f32");
     return DPPO_EINVAL;
   }
-  DPPO_TRY(require_mlp(h));
+  DPPO_TRY(require_tuned(h));
   if (!h->dims.continuous) {
     set_error("dppo_act_squash_f32 needs a continuous (Box) action space");
     return DPPO_EINVAL;
@@ -1204,7 +1234,7 @@ int dppo_actor_forward_f32(dppo_handle* h, const float* params, const float* obs
     set_error("invalid argument to dppo_actor_forward_f32");
     return DPPO_EINVAL;
   }
-  DPPO_TRY(require_mlp(h));
+  DPPO_TRY(require_tuned(h));
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   return launch_act(h->sh, h->po, params, obs, nullptr, n, 0, 0, S(stream), heads);
 }
@@ -1226,6 +1256,18 @@ int dppo_status(dppo_handle* h) {
     return DPPO_EINVAL;
   }
   return device_status(h);
+}
+
+int dppo_fused_plan(dppo_handle* h, int32_t m, int32_t* shape_class, int32_t* tile,
+                    int32_t* grid) {
+  if (!h || m < 0) {
+    set_error("invalid argument to dppo_fused_plan");
+    return DPPO_EINVAL;
+  }
+  if (shape_class) *shape_class = !h->mlp_ok ? 0 : h->wide ? 2 : 1;
+  if (tile) *tile = h->mlp_ok && h->wide ? wide_tile() : 0;
+  if (grid) *grid = h->mlp_ok ? fused_mb_grid(h->sh, m) : 0;
+  return DPPO_OK;
 }
 
 int dppo_fanin_selftest(dppo_handle* h, int32_t blocks, int32_t lds_bytes, int64_t timeout_us,

@@ -234,9 +234,12 @@ __device__ __forceinline__ bool grid_fanin(unsigned* ctr, unsigned epoch,
   return true;
 }
 
-// Default actor-critic MLP (hidden 64) kernels: mlp.hip.
+// Default actor-critic MLP kernels: mlp.hip (hidden 64, D <= 32: the tuned class) and mbwide.hip
+// (the wide class).
 struct MlpShape {
   int D, D8, A, continuous, R;  // R = record stride (floats)
+  int H;                        // hidden width
+  int cus;                      // compute units of the handle's device (wide grids; <= 0: 256)
 };
 size_t mlp_lds_bytes_eval(const MlpShape& sh);
 // Next-value reuse of the old-policy evaluation over a [T][row] rollout: where next_obs[i] is
@@ -302,6 +305,34 @@ int mbw_grid(int32_t m);
 size_t mbw_lds_bytes(const MlpShape& sh);
 int launch_mbw(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, int G,
                hipStream_t s);
+
+// Wide kernel family (mbwide.hip): hidden 128 with D <= 128, hidden 64 with 32 < D <= 128,
+// A <= 16.  One workgroup of H/16 waves per CU loops over 32-sample tiles and writes one slab;
+// wide_grid gives the workgroup count for a minibatch of m samples (at least two tiles each).
+bool tuned_shape(const MlpShape& sh);
+bool wide_shape(const MlpShape& sh);
+size_t wide_lds_bytes(const MlpShape& sh);
+int wide_tile();
+int wide_grid(const MlpShape& sh, int32_t m);
+int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, int G,
+                   hipStream_t s);
+int launch_wide_eval(const MlpShape& sh, const ParamOffsets& po, const float* params,
+                     const float* obs, const void* actions, const float* next_obs, float* logp,
+                     float* values, float* next_values, int64_t n, hipStream_t s);
+// pack_kernel's records without its LDS tile (which outgrows a CU past D = 32); mean_std = the
+// finalised advantage statistics (launch_stats_finalize)
+int launch_wide_pack(const PackArgs& a, const float* mean_std, hipStream_t s);
+// Shape-class dispatch: the tuned launchers above for tuned shapes, untouched; the wide family
+// otherwise.  capi.cpp calls only these.
+size_t fused_mb_lds_bytes(const MlpShape& sh);
+size_t fused_eval_lds_bytes(const MlpShape& sh);
+int fused_mb_grid(const MlpShape& sh, int32_t m, bool fused = false);
+int launch_fused_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, int G,
+                    hipStream_t s, const FusedAdam* fused = nullptr);
+int launch_fused_eval(const MlpShape& sh, const ParamOffsets& po, const float* params,
+                      const float* obs, const void* actions, const float* next_obs, float* logp,
+                      float* values, float* next_values, int64_t n, hipStream_t s,
+                      EvalReuse* reuse = nullptr);
 
 // Optimiser kernels: optim.hip.
 int slab_reduce_blocks(int64_t p_total);

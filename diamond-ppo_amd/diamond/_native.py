@@ -33,7 +33,7 @@ EXPORTED = [
     "dppo_perm_buffer", "dppo_perm_external", "dppo_perm_external_done", "dppo_get_trace", "dppo_perm_numpy", "dppo_comm_unique_id",
     "dppo_comm_init", "dppo_set_timing", "dppo_get_timing", "dppo_learn_targets_f32",
     "dppo_perm_targets_numpy", "dppo_perm_targets_numpy_par", "dppo_perm_par_stats", "dppo_perm_numpy_async", "dppo_perm_wait", "dppo_perm_stats", "dppo_perm_repin", "dppo_perm_domain", "dppo_perm_resolve", "dppo_perm_resolve_scratch", "dppo_perm_resolve_ex", "dppo_global_minibatch_lists", "dppo_act_f32", "dppo_act_squash_f32", "dppo_loopback_group",
-    "dppo_status", "dppo_fanin_selftest", "dppo_actor_forward_f32",
+    "dppo_status", "dppo_fanin_selftest", "dppo_fused_plan", "dppo_actor_forward_f32",
     "dppo_peer_export", "dppo_peer_open", "dppo_peer_close", "dppo_peer_allreduce", "dppo_peer_info",
     "dppo_peer_selftest",
     "dppo_gru_param_layout", "dppo_gru_create", "dppo_gru_destroy", "dppo_gru_minibatch_grad_f32",
@@ -160,6 +160,7 @@ def load():
         "dppo_status": (ctypes.c_int, [vp]),
         "dppo_actor_forward_f32": (ctypes.c_int, [vp, vp, vp, i64, vp, vp]),
         "dppo_fanin_selftest": (ctypes.c_int, [vp, i32, i32, i64, vp]),
+        "dppo_fused_plan": (ctypes.c_int, [vp, i32, vp, vp, vp]),
         "dppo_gru_param_layout": (ctypes.c_int, [P(GruDims), P(Layout)]),
         "dppo_gru_create": (ctypes.c_int, [ctypes.c_int, P(GruDims), P(vp)]),
         "dppo_gru_destroy": (None, [vp]),
@@ -400,6 +401,14 @@ class Handle:
 
     def set_gae_mode(self, mode: int):
         check(self.lib.dppo_set_gae_mode(self.h, int(mode)), "dppo_set_gae_mode")
+
+    def fused_plan(self, m: int) -> dict:
+        """{shape_class: None | "tuned" | "wide", tile, grid} of this handle for a minibatch of m
+        samples (dppo_fused_plan)."""
+        out = (ctypes.c_int32 * 3)()
+        base = ctypes.addressof(out)
+        check(self.lib.dppo_fused_plan(self.h, int(m), base, base + 4, base + 8), "dppo_fused_plan")
+        return {"shape_class": (None, "tuned", "wide")[out[0]], "tile": out[1], "grid": out[2]}
 
     def set_timing(self, enable: bool):
         check(self.lib.dppo_set_timing(self.h, int(bool(enable))), "dppo_set_timing")

@@ -17,9 +17,14 @@ only draws the swap targets and the GPU resolves the swaps (``shuffle.hip``,
 
 Two paths, chosen once per agent:
 
-* **fused** -- default network at supported sizes (hidden 64, obs_dim <= 32, actions <= 16):
-  everything in ``dppo_learn_f32`` (old-policy eval, GAE, normalisation, E x M fused
-  minibatch steps with clip + Adam, RCCL all-reduces when sharded).
+* **fused** -- default network at supported sizes: everything in ``dppo_learn_f32`` (old-policy
+  eval, GAE, normalisation, E x M fused minibatch steps with clip + Adam, RCCL all-reduces when
+  sharded).  Two shape classes (``fused_shape_class``), actions <= 16 in both:
+  **tuned** -- hidden 64, obs_dim <= 32: the register-resident kernels, and ``act()`` samples the
+  rollout's actions in HIP too;
+  **wide** -- hidden 128 with obs_dim <= 128, or hidden 64 with 32 < obs_dim <= 128, one rank
+  (``csrc/mbwide.hip``): the same learn, while rollouts sample with ``network.get_actions`` as
+  the reference does.  ``DPPO_WIDE=0`` sends wide shapes down the generic path (A/B runs).
 * **generic** -- any other ``network_cls`` (reference readme.md:89-111): the network's own
   methods run forward/backward under torch autograd on the GPU; GAE, advantage statistics and
   normalisation, and clip + Adam run in the HIP kernels (SURVEY.md §7.2 hard part 7).
@@ -339,6 +344,21 @@ class _DraftWorker:
             del fn, done
 
 
+def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1):
+    """Which fused kernel family serves the default network at this shape: ``"tuned"`` (hidden 64,
+    obs_dim <= 32), ``"wide"`` (hidden 128 with obs_dim <= 128, or hidden 64 with
+    32 < obs_dim <= 128; one rank only) or ``None`` (the generic path).  The same predicate as
+    ``dppo_create`` (csrc/capi.cpp).  ``DPPO_WIDE=0`` turns the wide class off."""
+    if not (1 <= act_dim <= 16 and obs_dim >= 1):
+        return None
+    if hidden == 64 and obs_dim <= 32:
+        return "tuned"
+    if obs_dim <= 128 and (hidden == 128 or hidden == 64) and world == 1 \
+            and os.environ.get("DPPO_WIDE", "1") != "0":
+        return "wide"
+    return None
+
+
 class NativeLearner:
     """Binds one agent (network + Adam) to a libdppo handle for its rollout shape."""
 
@@ -369,8 +389,12 @@ class NativeLearner:
         shapes_ok = network_is_default and L.count == len(names) and all(
             tuple(p.shape) in ((L.rows[i], L.cols[i]), (L.rows[i],)) for i, (_, p) in
             enumerate(network.named_parameters()))
-        self.fused = bool(shapes_ok and cfg.network_hidden_dim == 64 and obs_dim <= 32
-                          and act_dim <= 16)
+        self.shape_class = (fused_shape_class(int(cfg.network_hidden_dim), obs_dim, act_dim,
+                                              self.world) if shapes_ok else None)
+        self.fused = self.shape_class is not None
+        # the fused actor kernels (act()) exist for the tuned class only: wide shapes sample
+        # their rollouts with network.get_actions, as the reference does
+        self.fused_act = self.shape_class == "tuned"
         if self.fused:
             self.flat = FlatParams(network, device, [L.offset[i] for i in range(L.count)], L.total)
         else:
@@ -523,7 +547,7 @@ class NativeLearner:
         ``squash`` (continuous only, the tanh-squash extension): ``True`` for tanh(u), or a
         ``(low, high)`` pair of A-float bounds; then the same kernel launch also emits the
         environment's actions (``dppo_act_squash_f32``) and ``(u, env_actions)`` is returned."""
-        if not self.fused:
+        if not self.fused_act:
             raise RuntimeError("act() needs the default network (fused path)")
         if squash is not None and squash is not False:
             return self._act_squash(observations, seed, squash)

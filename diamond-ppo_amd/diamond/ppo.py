@@ -184,7 +184,7 @@ class _AgentBase:
             stager.begin()
         squash = self._squash_spec()
         for t in range(self.cfg.rollout_steps):
-            if self.fused_actions and self._learner.fused:
+            if self.fused_actions and self._learner.fused_act:
                 if squash is None:
                     actions = self._learner.act(observations, self._act_seed)
                     env_actions = actions

@@ -35,7 +35,9 @@ extern "C" {
 #define DPPO_OK 0
 #define DPPO_EINVAL (-1)       /* invalid argument (Python: ValueError / AssertionError) */
 #define DPPO_EHIP (-2)         /* HIP runtime error (Python: RuntimeError) */
-#define DPPO_EUNSUPPORTED (-3) /* shape outside the fused kernels' support (Python: NotImplementedError) */
+#define DPPO_EUNSUPPORTED (-3) /* shape outside the fused kernels' support -- neither the tuned nor the wide
+                                  class of dims.hidden, or an actor call at a wide shape (Python:
+                                  NotImplementedError) */
 #define DPPO_ENOMEM (-4)       /* workspace allocation failed (Python: MemoryError) */
 #define DPPO_ECOMM (-5)        /* RCCL failure (Python: RuntimeError) */
 
@@ -57,7 +59,9 @@ typedef struct dppo_dims {
   int32_t obs_dim;         /* D = prod(observation_space.shape)        (ppo.py:54) */
   int32_t act_dim;         /* discrete: action_space.n; continuous: prod(action_space.shape) */
   int32_t continuous;      /* 0 = PPO/Categorical, 1 = ContinuousPPO/JointNormal */
-  int32_t hidden;          /* network_hidden_dim (ppo.py:32,51) */
+  int32_t hidden;          /* network_hidden_dim (ppo.py:32,51).  Fused kernels, act_dim <= 16: the tuned
+                              class at 64 with obs_dim <= 32; the wide class (world_size 1; no actor
+                              calls) at 128 with obs_dim <= 128 and at 64 with 32 < obs_dim <= 128 */
   int32_t num_epochs;      /* ppo.py:25 */
   int32_t num_minibatches; /* ppo.py:26 */
   int32_t world_size;      /* ranks sharing the env axis (1 = single GPU) */
@@ -402,6 +406,13 @@ int dppo_status(dppo_handle* h);
  * timeout and sets the sticky error (dppo_status).  Stream-ordered. */
 int dppo_fanin_selftest(dppo_handle* h, int32_t blocks, int32_t lds_bytes, int64_t timeout_us,
                         void* stream);
+
+/* Which fused kernel family serves this handle and how it would cut a minibatch of m samples:
+ * *shape_class = 0 (none: the MLP entry points return DPPO_EUNSUPPORTED), 1 (tuned) or 2 (wide);
+ * *grid = workgroups (= gradient slabs) of the minibatch kernel for m samples, before the clamp to
+ * the handle's own grid; *tile = samples per tile of the wide kernel, whose workgroup b runs tiles
+ * b, b + grid, ... (0 for the other classes).  Any output pointer may be NULL.  Host only. */
+int dppo_fused_plan(dppo_handle* h, int32_t m, int32_t* shape_class, int32_t* tile, int32_t* grid);
 
 /* Single-device loopback group (parity tests of the data-parallel path without a second GPU;
  * RCCL refuses two ranks on one device): hs[r] must be rank r of world_size n (dppo_dims), all on
