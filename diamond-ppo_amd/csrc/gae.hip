@@ -11,7 +11,9 @@
 // flops per step; the bytes are what cost.  gae_pipe_kernel (below) overlaps the loads, the scan
 // and the stores of one env tile; gae_kernel is the plain stage-all / scan / store-all form, kept
 // for unaligned shapes (N not a multiple of 16 or unaligned buffers).
+#include <charconv>
 #include <cstdlib>
+#include <system_error>
 
 #include "common.h"
 
@@ -1040,6 +1042,19 @@ int launch_pipe(int nt, int grid, hipStream_t s, const float* r, const uint8_t* 
   }
 }
 
+// The config's Python float behind a C-ABI float.  The reference multiplies cfg.gamma *
+// cfg.gae_lambda as doubles (ppo.py:214-216), and (double)0.9f is not 0.9: the product of the
+// widened floats rounds to another float32 for about a third of the (gamma, lambda) pairs of two
+// or three digits (0.9 * 0.8 among them; 0.99 * 0.95 not).  The shortest decimal that reads back
+// as the same float is the config's own value whenever that was written with up to seven digits.
+static double config_double(float x) {
+  char buf[32];
+  const auto w = std::to_chars(buf, buf + sizeof buf, x);
+  double d = (double)x;
+  if (w.ec == std::errc()) std::from_chars(buf, w.ptr, d);
+  return d;
+}
+
 int launch_gae(const float* r, const uint8_t* te, const uint8_t* tr, const float* v,
                const float* nv, float* adv, float* ret, double* partials, int T, int N,
                float gamma, float gae_lambda, hipStream_t s, int* n_partials, int mode) {
@@ -1047,7 +1062,7 @@ int launch_gae(const float* r, const uint8_t* te, const uint8_t* tr, const float
   *n_partials = G;
   if (T <= 0 || N <= 0) return DPPO_OK;
   // Python evaluates gamma * gae_lambda first, in double (ppo.py:214-216).
-  const float c = (float)((double)gamma * (double)gae_lambda);
+  const float c = (float)(config_double(gamma) * config_double(gae_lambda));
   const bool vec = (N % kEnvTile) == 0 && ((uintptr_t)r % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
                    ((uintptr_t)nv % 16 == 0) && ((uintptr_t)adv % 16 == 0) &&
                    ((uintptr_t)ret % 16 == 0) && ((uintptr_t)te % 16 == 0) &&

@@ -130,7 +130,9 @@ void dppo_destroy(dppo_handle* h);
 
 /* GAE over the [T][N] buffers: replaces PPO.calculate_advantage (ppo.py:188-222; identical in
  * continuous_ppo.py:200-234, recurrent_ppo.py:265-299) fused with returns = values + adv
- * (ppo.py:241).  Bit-exact with the reference's fp32 op order.  Also records the per-tile
+ * (ppo.py:241).  Bit-exact with the reference's fp32 op order; gamma * gae_lambda is taken as the
+ * reference takes it, in double from the config's values (each float's shortest decimal), which
+ * is exact for values of up to seven significant digits.  Also records the per-tile
  * (sum, sum of squares) partials the next call reduces. */
 int dppo_gae_f32(dppo_handle* h, const float* rewards, const uint8_t* term, const uint8_t* trunc,
                  const float* values, const float* next_values, float* adv, float* returns,
