@@ -87,8 +87,7 @@ struct dppo_handle {
   dppo_layout layout{};
   ParamOffsets po{};
   MlpShape sh{};
-  bool mlp_ok = false;  // a fused kernel family applies: tuned or wide
-  bool wide = false;    // ... the wide one (mbwide.hip)
+  ShapeClass cls = kShapeNone;  // the fused kernel family that applies (require_mlp)
   int64_t B = 0;   // local samples T*N
   int32_t mb = 0;  // local minibatch size B / M
   // global-minibatch data parallelism (dims.global_minibatches with world_size > 1): the host
@@ -379,7 +378,7 @@ struct Timed {
 };
 
 int require_mlp(const dppo_handle* h) {
-  if (!h->mlp_ok) {
+  if (h->cls == kShapeNone) {
     set_error("fused MLP kernels support act_dim<=16 with hidden=64, obs_dim<=32 (tuned) or, on "
               "one rank, hidden=128, obs_dim<=128 / hidden=64, 32<obs_dim<=128 (wide) "
               "(got H=%d D=%d A=%d world=%d)",
@@ -392,7 +391,7 @@ int require_mlp(const dppo_handle* h) {
 // Rollout sampling (act kernels) exists for the tuned class only.
 int require_tuned(const dppo_handle* h) {
   DPPO_TRY(require_mlp(h));
-  if (h->wide) {
+  if (h->cls != kShapeTuned) {
     set_error("the fused actor kernels support hidden=64, obs_dim<=32, act_dim<=16 only "
               "(got H=%d D=%d A=%d): sample wide shapes with the network itself",
               h->dims.hidden, h->dims.obs_dim, h->dims.act_dim);
@@ -476,19 +475,25 @@ unsigned next_xseq(dppo_handle* h) {
   return h->xseq;
 }
 
-int peer_allreduce(dppo_handle* h, void* buf, size_t n, bool f64, hipStream_t s) {
+// The handle's side of a peer exchange, but for the exchange's own seq (and src / dst / n).
+PeerArgs peer_args(const dppo_handle* h) {
   PeerArgs a{};
-  a.src = buf;
-  a.dst = buf;
   for (int r = 0; r < h->xworld; ++r) a.bufs[r] = h->xpeer[r];
-  a.n = (int64_t)n;
   a.data_bytes = h->xcap * 8;
   a.world = h->xworld;
   a.rank = h->rank;
-  a.seq = next_xseq(h);
   a.err = h->err_dev;
   a.timeout_ticks = h->xticks;
   a.acq = peer_acq();
+  return a;
+}
+
+int peer_allreduce(dppo_handle* h, void* buf, size_t n, bool f64, hipStream_t s) {
+  PeerArgs a = peer_args(h);
+  a.src = buf;
+  a.dst = buf;
+  a.n = (int64_t)n;
+  a.seq = next_xseq(h);
   return launch_peer_sum(a, f64, s);
 }
 
@@ -535,7 +540,8 @@ int prepare(dppo_handle* h, const dppo_rollout* ro, const float* params, const d
   // or unaligned buffers: one partial per 16 envs, 4,096 at N = 65,536) would be ~128 MB of
   // redundant L2 reads per learn -- there the separate reduction launch is cheaper.
   const bool fold_stats =
-      hp->advantage_norm && !distributed(h) && !stats_launch && h->n_partials <= 512 && !h->wide;
+      hp->advantage_norm && !distributed(h) && !stats_launch && h->n_partials <= 512 &&
+      h->cls != kShapeWide;
   if (hp->advantage_norm && !fold_stats) {
     {
       Timed tm(h, K_STATS, s);
@@ -566,7 +572,7 @@ int prepare(dppo_handle* h, const dppo_rollout* ro, const float* params, const d
   pa.A = d.act_dim;
   pa.R = h->sh.R;
   pa.continuous = d.continuous;
-  if (h->wide) {
+  if (h->cls == kShapeWide) {
     // pack_kernel's LDS tile outgrows a CU past D = 32: the wide class packs straight from global
     // memory, with the statistics finalised by a launch of their own (the same operations)
     if (hp->advantage_norm) {
@@ -596,36 +602,99 @@ int prepare(dppo_handle* h, const dppo_rollout* ro, const float* params, const d
   return DPPO_OK;
 }
 
-// One minibatch: fused gradient kernel -> slab reduction -> [all-reduce] (grad left in h->grad).
-int minibatch_grad(dppo_handle* h, const float* params, const int32_t* idx, const int32_t* seg,
-                   int32_t m, int32_t m_total, const dppo_hparams* hp, hipStream_t s) {
+// The continuous head's entropy constant for whoever reduces this handle's slabs: on rank 0 only,
+// so that it enters a cross-rank sum once.
+LogStdTerm log_std_term(const dppo_handle* h, const dppo_hparams* hp) {
   const dppo_dims& d = h->dims;
-  GradArgs ga{};
-  ga.params = params;
-  ga.rec = h->rec;
+  return {h->po.ls, d.continuous ? d.act_dim : 0, hp->entropy_beta,
+          (d.continuous && h->rank == 0) ? 1 : 0};
+}
+
+// Optimizer step number `step` (1, 2, ...) on params / m / v: the bias corrections in double, as
+// torch's _single_tensor_adam computes them, then rounded once.
+AdamStep make_adam_step(const dppo_hparams* hp, int64_t step, float* params, float* m, float* v,
+                        float* trace, float inv_m) {
+  const double bc1 = 1.0 - std::pow((double)hp->adam_beta1, (double)step);
+  const double bc2 = 1.0 - std::pow((double)hp->adam_beta2, (double)step);
+  const double step_size = hp->lr / bc1;
+  const double bc2_sqrt = std::pow(bc2, 0.5);
+  return {params, m, v, hp->grad_norm_clip, (float)(-step_size), (float)bc2_sqrt,
+          hp->adam_beta1, hp->adam_beta2, hp->adam_eps, trace, inv_m, hp->value_loss_weight,
+          hp->entropy_beta};
+}
+
+// DPPO_FUSED_ADAM=1: the same step as the minibatch kernel's own tail (launch h->fused_epoch + 1).
+FusedAdam fused_adam(dppo_handle* h, const AdamStep& st, const LogStdTerm& ls) {
+  FusedAdam fa{};
+  fa.grad = h->grad;
+  fa.sq_part = h->sq_part;
+  fa.arrivals = h->arrivals + kArrivalWords;
+  fa.epoch = ++h->fused_epoch;
+  fa.err = h->err_dev;
+  fa.timeout_ticks = h->fanin_ticks;
+  fa.params = st.params;
+  fa.m = st.m;
+  fa.v = st.v;
+  fa.max_norm = st.max_norm;
+  fa.neg_step_size = st.neg_step_size;
+  fa.bc2_sqrt = st.bc2_sqrt;
+  fa.beta1 = st.beta1;
+  fa.beta2 = st.beta2;
+  fa.eps = st.eps;
+  fa.trace = st.trace;
+  fa.ls_off = ls.ls_off;
+  fa.ls_n = ls.ls_n;
+  fa.add_entropy_const = ls.add_entropy_const;
+  return fa;
+}
+
+// What the minibatch kernel launches of one call share: the kernel, its grid, and its arguments
+// but for the minibatch's own idx / seg.
+struct GradPlan {
+  MbKernel kernel;
+  int G;
+  GradArgs ga;
+};
+
+// Minibatches of m local samples out of m_total over all ranks; `segmented`: given as device
+// {start, end} segments (global minibatches), of up to the handle's largest share.
+GradPlan grad_plan(const dppo_handle* h, const float* params, int32_t m, int32_t m_total,
+                   const dppo_hparams* hp, bool fused_tail, bool segmented) {
+  GradPlan gp{};
+  gp.kernel = pick_mb_kernel(h->sh, fused_tail);
+  // with segments the size is known only on the device: the handle's grid (sized for the largest
+  // share a rank can hold) -- workgroups past the last step contribute zero slabs
+  gp.G = segmented ? h->G : std::min(fused_mb_grid(gp.kernel, h->sh, m), h->G);
+  gp.ga.params = params;
+  gp.ga.rec = h->rec;
+  gp.ga.m = m;
+  gp.ga.inv_m = (float)(1.0 / (double)m_total);
+  gp.ga.clip_eps = hp->ppo_clip;
+  gp.ga.vf_coef = hp->value_loss_weight;
+  gp.ga.ent_coef = hp->entropy_beta;
+  gp.ga.slabs = h->slabs;
+  gp.ga.slab_stride = h->slab_stride;
+  gp.ga.p_total = h->layout.total;
+  return gp;
+}
+
+int launch_grad(dppo_handle* h, const GradPlan& gp, const int32_t* idx, const int32_t* seg,
+                const FusedAdam* fused, hipStream_t s) {
+  GradArgs ga = gp.ga;
   ga.idx = idx;
   ga.seg = seg;
-  ga.m = m;
-  ga.inv_m = (float)(1.0 / (double)m_total);
-  ga.clip_eps = hp->ppo_clip;
-  ga.vf_coef = hp->value_loss_weight;
-  ga.ent_coef = hp->entropy_beta;
-  ga.slabs = h->slabs;
-  ga.slab_stride = h->slab_stride;
-  ga.p_total = h->layout.total;
-  // with `seg` the size is known only on the device: the handle's grid (sized for the largest
-  // share a rank can hold) -- workgroups past the last step contribute zero slabs
-  int G = seg ? h->G : fused_mb_grid(h->sh, m);
-  if (G > h->G) G = h->G;
-  {
-    Timed tm(h, K_GRAD, s);
-    DPPO_TRY(launch_fused_mb(h->sh, h->po, ga, G, s));
-  }
+  Timed tm(h, K_GRAD, s);
+  return launch_fused_mb(gp.kernel, h->sh, h->po, ga, gp.G, s, fused);
+}
+
+// One minibatch: fused gradient kernel -> slab reduction -> [all-reduce] (grad left in h->grad).
+int minibatch_grad(dppo_handle* h, const GradPlan& gp, const LogStdTerm& ls, const int32_t* idx,
+                   const int32_t* seg, hipStream_t s) {
+  DPPO_TRY(launch_grad(h, gp, idx, seg, nullptr, s));
   {
     Timed tm(h, K_REDUCE, s);
-    DPPO_TRY(launch_slab_reduce(h->slabs, G, h->slab_stride, h->layout.total, h->grad, h->sq_part,
-                                h->po.ls, d.continuous ? d.act_dim : 0, hp->entropy_beta,
-                                (d.continuous && h->rank == 0) ? 1 : 0, s));
+    DPPO_TRY(launch_slab_reduce(h->slabs, gp.G, h->slab_stride, h->layout.total, h->grad,
+                                h->sq_part, ls, s));
   }
   if (distributed(h)) {
     Timed tm(h, K_COMM, s, true);
@@ -744,128 +813,69 @@ int learn_impl(dppo_handle* h, const dppo_rollout* rollout, float* params, float
                                  d.num_envs * h->nranks, d.num_envs * h->rank, d.num_envs,
                                  (int32_t)E, (int32_t)M, s));
   }
-  // (6) E x M dependent optimizer steps (ppo.py:258-285)
+  // (6) E x M dependent optimizer steps (ppo.py:258-285).  What they share is resolved here, once
+  // per learn (the two switches are read now: tests flip them between learns of one process).
   const int32_t mb = h->mb;
   // global minibatch size: the divisor of every mean (ppo.py:270-274)
   const int32_t m_total = h->gmb ? (int32_t)(h->Bg / M) : mb * world_of(h);
-  const float inv_m = (float)(1.0 / (double)m_total);
+  // The Adam path.  Default: minibatch kernel -> reduce_adam (slab reduce + clip + Adam), one
+  // launch each.  Over a peer exchange the cross-rank sum runs inside reduce_adam_kernel (each
+  // block publishes its slice and sums the ranks' slices before the norm), so that multi-rank
+  // learn keeps this sequence.
+  // `multi`: the exchanging sequence -- minibatch kernel, slab reduction, [all-reduce], clip +
+  // Adam kernel -- for every other communicator, for a device that cannot hold
+  // reduce_adam_kernel's grid at once, and under DPPO_SPLIT_ADAM=1 (parity tests: the N > 1
+  // kernels checked against the reference traces on one device).
+  // DPPO_FUSED_ADAM=1 (single rank, tuned class): the slab reduction, clip and Adam as the
+  // minibatch kernel's own tail (one launch per minibatch, two grid fan-ins).  Measured: the tail
+  // costs what reduce_adam_kernel does (~8 us: the fan-ins, not the launch, dominate), throughput
+  // within ~1.5 %; the separate kernel stays the default (and keeps the minibatch kernel's
+  // roofline its own).
+  const bool split = std::getenv("DPPO_SPLIT_ADAM") != nullptr;
+  const bool peer = h->xworld > 0 && h->xfused && h->radam_ok && !split;
+  const bool multi = (distributed(h) && !peer) || !h->radam_ok || split;
+  const bool fused_tail = !multi && !peer && h->cls != kShapeWide &&
+                          std::getenv("DPPO_FUSED_ADAM") != nullptr;
+  const GradPlan gp = grad_plan(h, params, mb, m_total, hp, fused_tail, h->gmb);
+  const LogStdTerm ls = log_std_term(h, hp);
+  PeerArgs pa = peer ? peer_args(h) : PeerArgs{};
+  // a block's intra-device fan-in starts after its peer wait: bound it like the peer wait
+  const unsigned long long fan_ticks =
+      peer && h->xticks > h->fanin_ticks ? h->xticks : h->fanin_ticks;
+#ifdef DPPO_ABL_RADAM_G1
+  const int Gr = 1;  // timing-only ablation: the fixed cost of the launch without slab reads
+#elif defined(DPPO_ABL_HALF_SLABS)
+  const int Gr = (gp.G + 1) / 2;  // timing-only: half the slab bytes (mbwave.hip ablation)
+#else
+  const int Gr = gp.G;
+#endif
   for (int64_t e = 0; e < E; ++e) {
     for (int64_t j = 0; j < M; ++j) {
       const int64_t k = e * M + j;
       const int32_t* idx =
           h->gmb ? h->perms_local + e * h->B : h->perms_dev + e * h->B + j * mb;
       const int32_t* seg = h->gmb ? h->seg + e * (M + 1) + j : nullptr;
-      const double step = (double)(hp->adam_step + k + 1);
-      const double bc1 = 1.0 - std::pow((double)hp->adam_beta1, step);
-      const double bc2 = 1.0 - std::pow((double)hp->adam_beta2, step);
-      const double step_size = hp->lr / bc1;
-      const double bc2_sqrt = std::pow(bc2, 0.5);
-      float* trace = h->trace + k * DPPO_TRACE_FIELDS;
-      // DPPO_SPLIT_ADAM=1 (parity tests): the multi-rank sequence -- minibatch kernel, slab
-      // reduction, [all-reduce], clip + Adam kernel -- on one device, so the N > 1 kernels are
-      // checked against the reference traces without a second GPU
-      // A device that cannot hold reduce_adam_kernel's grid at once takes the same sequence.
-      // Over a peer exchange the cross-rank sum runs inside reduce_adam_kernel (each block
-      // publishes its slice and sums the ranks' slices before the norm), so the multi-rank learn
-      // keeps the single-device sequence: minibatch kernel -> reduce_adam, one launch each.
-      const bool split = std::getenv("DPPO_SPLIT_ADAM") != nullptr;
-      const bool peer = h->xworld > 0 && h->xfused && h->radam_ok && !split;
-      const bool multi = (distributed(h) && !peer) || !h->radam_ok || split;
-      if (!multi) {
-        // single device (or peer exchange): fused kernel -> slab reduce + clip + Adam in one launch
-        GradArgs ga{};
-        ga.params = params;
-        ga.rec = h->rec;
-        ga.idx = idx;
-        ga.seg = seg;
-        ga.m = mb;
-        ga.inv_m = inv_m;
-        ga.clip_eps = hp->ppo_clip;
-        ga.vf_coef = hp->value_loss_weight;
-        ga.ent_coef = hp->entropy_beta;
-        ga.slabs = h->slabs;
-        ga.slab_stride = h->slab_stride;
-        ga.p_total = h->layout.total;
-        const bool fused_tail = std::getenv("DPPO_FUSED_ADAM") != nullptr && !peer && !h->wide;
-        // with `seg` (global minibatches) the share is known only on the device: the handle's
-        // grid, as minibatch_grad
-        int G = seg ? h->G : fused_mb_grid(h->sh, mb, fused_tail);
-        if (G > h->G) G = h->G;
-        // DPPO_FUSED_ADAM=1: the slab reduction, clip and Adam as the minibatch kernel's own
-        // tail (one launch per minibatch, two grid fan-ins).  Measured: the tail costs what
-        // reduce_adam_kernel does (~8 us: the fan-ins, not the launch, dominate), throughput
-        // within ~1.5 %; the separate kernel stays the default (and keeps the minibatch kernel's
-        // roofline its own).
-        if (fused_tail) {
-          FusedAdam fa{};
-          fa.grad = h->grad;
-          fa.sq_part = h->sq_part;
-          fa.arrivals = h->arrivals + kArrivalWords;
-          fa.epoch = ++h->fused_epoch;
-          fa.err = h->err_dev;
-          fa.timeout_ticks = h->fanin_ticks;
-          fa.params = params;
-          fa.m = adam_m;
-          fa.v = adam_v;
-          fa.max_norm = hp->grad_norm_clip;
-          fa.neg_step_size = (float)(-step_size);
-          fa.bc2_sqrt = (float)bc2_sqrt;
-          fa.beta1 = hp->adam_beta1;
-          fa.beta2 = hp->adam_beta2;
-          fa.eps = hp->adam_eps;
-          fa.trace = trace;
-          fa.ls_off = h->po.ls;
-          fa.ls_n = d.continuous ? d.act_dim : 0;
-          fa.add_entropy_const = d.continuous ? 1 : 0;
-          Timed tm(h, K_GRAD, s);
-          DPPO_TRY(launch_fused_mb(h->sh, h->po, ga, G, s, &fa));
-          continue;
-        }
-        {
-          Timed tm(h, K_GRAD, s);
-          DPPO_TRY(launch_fused_mb(h->sh, h->po, ga, G, s));
-        }
+      const AdamStep st = make_adam_step(hp, hp->adam_step + k + 1, params, adam_m, adam_v,
+                                         h->trace + k * DPPO_TRACE_FIELDS, gp.ga.inv_m);
+      if (multi) {
+        DPPO_TRY(minibatch_grad(h, gp, ls, idx, seg, s));
+        Timed tm(h, K_ADAM, s);
+        // after the all-reduce the reduce kernel's per-block norm partials are stale: the Adam
+        // kernel recomputes the norm from the gradient itself (every block, in one fixed order;
+        // measured cheaper than the grid fan-in of reduce_adam_kernel over the reduced gradient)
+        DPPO_TRY(launch_clip_adam_traced(st, h->grad, h->layout.total, nullptr,
+                                         slab_reduce_blocks(h->layout.total), nullptr, s));
+      } else if (fused_tail) {
+        const FusedAdam fa = fused_adam(h, st, ls);
+        DPPO_TRY(launch_grad(h, gp, idx, seg, &fa, s));
+      } else {
+        DPPO_TRY(launch_grad(h, gp, idx, seg, nullptr, s));
         Timed tm(h, K_RADAM, s);
-#ifdef DPPO_ABL_RADAM_G1
-        const int Gr = 1;  // timing-only ablation: the fixed cost of the launch without slab reads
-#elif defined(DPPO_ABL_HALF_SLABS)
-        const int Gr = (G + 1) / 2;  // timing-only: half the slab bytes (mbwave.hip ablation)
-#else
-        const int Gr = G;
-#endif
-        PeerArgs pa{};
-        if (peer) {
-          for (int r = 0; r < h->xworld; ++r) pa.bufs[r] = h->xpeer[r];
-          pa.data_bytes = h->xcap * 8;
-          pa.world = h->xworld;
-          pa.rank = h->rank;
-          pa.seq = next_xseq(h);
-          pa.err = h->err_dev;
-          pa.timeout_ticks = h->xticks;
-          pa.acq = peer_acq();
-        }
-        // a block's intra-device fan-in starts after its peer wait: bound it like the peer wait
-        const unsigned long long fan_ticks =
-            peer && h->xticks > h->fanin_ticks ? h->xticks : h->fanin_ticks;
-        DPPO_TRY(launch_reduce_adam(
-            h->slabs, Gr, h->slab_stride, h->layout.total, h->grad, h->ra_tags, h->po.ls,
-            d.continuous ? d.act_dim : 0, hp->entropy_beta,
-            (d.continuous && h->rank == 0) ? 1 : 0, next_radam_epoch(h), params, adam_m,
-            adam_v, hp->grad_norm_clip, (float)(-step_size), (float)bc2_sqrt,
-            hp->adam_beta1, hp->adam_beta2, hp->adam_eps, trace, inv_m, hp->value_loss_weight,
-            hp->entropy_beta, h->err_dev, fan_ticks, s, peer ? &pa : nullptr));
-        continue;
+        if (peer) pa.seq = next_xseq(h);
+        DPPO_TRY(launch_reduce_adam(h->slabs, Gr, h->slab_stride, h->layout.total, h->grad,
+                                    h->ra_tags, ls, next_radam_epoch(h), st, h->err_dev, fan_ticks,
+                                    s, peer ? &pa : nullptr));
       }
-      DPPO_TRY(minibatch_grad(h, params, idx, seg, mb, m_total, hp, s));
-      Timed tm(h, K_ADAM, s);
-      // after the all-reduce the reduce kernel's per-block norm partials are stale: the Adam
-      // kernel recomputes the norm from the gradient itself (every block, in one fixed order;
-      // measured cheaper than the grid fan-in of reduce_adam_kernel over the reduced gradient)
-      DPPO_TRY(launch_clip_adam_traced(params, h->grad, adam_m, adam_v, h->layout.total, nullptr,
-                                       slab_reduce_blocks(h->layout.total), hp->grad_norm_clip,
-                                       (float)(-step_size), (float)bc2_sqrt, hp->adam_beta1,
-                                       hp->adam_beta2, hp->adam_eps, nullptr, trace, inv_m,
-                                       hp->value_loss_weight, hp->entropy_beta, s));
     }
   }
   // device slot ds may be overwritten by an upload once this learn's minibatches are done
@@ -921,10 +931,12 @@ int dppo_create(int device, const dppo_dims* dims, dppo_handle** out) {
   h->sh.H = dims->hidden;
   // tuned class (hidden 64, D <= 32): the minibatch kernels build a slab image in LDS; wide class
   // (mbwide.hip): single rank only -- multi-rank wide learns stay with the caller's generic path
-  h->wide = !tuned_shape(h->sh) && wide_shape(h->sh) && dims->world_size == 1 &&
-            wide_lds_bytes(h->sh) <= 160 * 1024;
-  h->mlp_ok = h->wide || (tuned_shape(h->sh) && mb_lds_bytes(h->sh) <= 160 * 1024 &&
-                          (size_t)(h->layout.total + 8) * 4 <= 160 * 1024);
+  if (tuned_shape(h->sh)) {
+    if (mb_lds_bytes(h->sh) <= 160 * 1024 && (size_t)(h->layout.total + 8) * 4 <= 160 * 1024)
+      h->cls = kShapeTuned;
+  } else if (wide_shape(h->sh) && dims->world_size == 1 && wide_lds_bytes(h->sh) <= 160 * 1024) {
+    h->cls = kShapeWide;
+  }
   // One fused-minibatch workgroup per CU (its LDS footprint admits exactly one): never launch
   // more workgroups than CUs, or the surplus runs as a second, serialised round.
   int cus = 0;
@@ -934,11 +946,12 @@ int dppo_create(int device, const dppo_dims* dims, dppo_handle** out) {
   h->num_cus = cus;
   h->sh.cus = cus;
   // global minibatches: a rank's share of one varies around mb; size the grid for a whole one
-  // (the larger of the two kernels' grids: DPPO_FUSED_ADAM runs the two-team kernel)
+  // (the larger grid of the kernels a learn may pick: with and without the fused Adam tail)
   {
     const int32_t mg = h->gmb ? (int32_t)std::min<int64_t>(h->Bg / dims->num_minibatches, h->B)
                               : (h->mb > 0 ? h->mb : 1);
-    h->G = std::max(fused_mb_grid(h->sh, mg), fused_mb_grid(h->sh, mg, true));
+    h->G = std::max(fused_mb_grid(pick_mb_kernel(h->sh, false), h->sh, mg),
+                    fused_mb_grid(pick_mb_kernel(h->sh, true), h->sh, mg));
   }
   if (h->G > cus) h->G = cus;
   h->slab_stride = round_up(h->layout.total + 8, 64);
@@ -1264,9 +1277,10 @@ int dppo_fused_plan(dppo_handle* h, int32_t m, int32_t* shape_class, int32_t* ti
     set_error("invalid argument to dppo_fused_plan");
     return DPPO_EINVAL;
   }
-  if (shape_class) *shape_class = !h->mlp_ok ? 0 : h->wide ? 2 : 1;
-  if (tile) *tile = h->mlp_ok && h->wide ? wide_tile() : 0;
-  if (grid) *grid = h->mlp_ok ? fused_mb_grid(h->sh, m) : 0;
+  if (shape_class) *shape_class = h->cls;
+  if (tile) *tile = h->cls == kShapeWide ? wide_tile() : 0;
+  if (grid)
+    *grid = h->cls != kShapeNone ? fused_mb_grid(pick_mb_kernel(h->sh, false), h->sh, m) : 0;
   return DPPO_OK;
 }
 
@@ -1296,7 +1310,8 @@ int dppo_minibatch_grad_f32(dppo_handle* h, const float* params, const int32_t* 
   DPPO_TRY(require_mlp(h));
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   hipStream_t s = S(stream);
-  DPPO_TRY(minibatch_grad(h, params, idx, nullptr, m, m_total, hp, s));
+  const GradPlan gp = grad_plan(h, params, m, m_total, hp, false, false);
+  DPPO_TRY(minibatch_grad(h, gp, log_std_term(h, hp), idx, nullptr, s));
   DPPO_HIP_CHECK(hipMemcpyAsync(grad, h->grad, (size_t)h->layout.total * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
   if (loss4) {
@@ -1322,12 +1337,14 @@ int dppo_clip_adam_f32(float* params, float* grad, float* adam_m, float* adam_v,
     set_error("invalid argument to dppo_clip_adam_f32");
     return DPPO_EINVAL;
   }
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  const double step_size = lr / bc1;
-  const double bc2_sqrt = std::pow(bc2, 0.5);
-  return launch_clip_adam(params, grad, adam_m, adam_v, n, max_norm, (float)(-step_size),
-                          (float)bc2_sqrt, beta1, beta2, eps, out_norm, S(stream));
+  dppo_hparams hp{};
+  hp.grad_norm_clip = max_norm;
+  hp.lr = lr;
+  hp.adam_beta1 = beta1;
+  hp.adam_beta2 = beta2;
+  hp.adam_eps = eps;
+  return launch_clip_adam_traced(make_adam_step(&hp, step, params, adam_m, adam_v, nullptr, 0.f),
+                                 grad, n, nullptr, 0, out_norm, S(stream));
 }
 
 
@@ -1866,19 +1883,14 @@ int dppo_peer_selftest(dppo_handle* h, void* stream) {
       for (int64_t i = 0; i < n; ++i)
         hf[i] = (float)((h->rank + 1) * (int)(i % 5 + 1) + 100 * k);
       DPPO_HIP_CHECK(hipMemcpyAsync(slab, hf.data(), n * 4, hipMemcpyHostToDevice, s));
-      PeerArgs pa{};
-      for (int r = 0; r < W; ++r) pa.bufs[r] = h->xpeer[r];
-      pa.data_bytes = h->xcap * 8;
-      pa.world = W;
-      pa.rank = h->rank;
+      PeerArgs pa = peer_args(h);
       pa.seq = next_xseq(h);
-      pa.err = h->err_dev;
-      pa.timeout_ticks = h->xticks;
-          pa.acq = peer_acq();
-      DPPO_TRY(launch_reduce_adam(slab, 1, h->slab_stride, P, grad, h->ra_tags, 0, 0, 0.f, 0,
-                                  next_radam_epoch(h), pm, pm + P, pm + 2 * P, 0.5f, -1e-3f, 1.f,
-                                  0.9f, 0.999f, 1e-5f, nullptr, 1.f, 1.f, 0.f, h->err_dev,
-                                  h->xticks, s, &pa));
+      // any step will do (only the exchanged gradient is checked): clip 0.5, step size 1e-3,
+      // bc2_sqrt 1, betas 0.9 / 0.999, eps 1e-5, no trace
+      const AdamStep st{pm, pm + P, pm + 2 * P, 0.5f, -1e-3f, 1.f, 0.9f, 0.999f,
+                        1e-5f, nullptr, 1.f, 1.f, 0.f};
+      DPPO_TRY(launch_reduce_adam(slab, 1, h->slab_stride, P, grad, h->ra_tags, LogStdTerm{},
+                                  next_radam_epoch(h), st, h->err_dev, h->xticks, s, &pa));
       DPPO_HIP_CHECK(hipMemcpyAsync(hf.data(), grad, n * 4, hipMemcpyDeviceToHost, s));
       DPPO_HIP_CHECK(hipStreamSynchronize(s));
       DPPO_TRY(device_status(h));

@@ -241,7 +241,6 @@ struct MlpShape {
   int H;                        // hidden width
   int cus;                      // compute units of the handle's device (wide grids; <= 0: 256)
 };
-size_t mlp_lds_bytes_eval(const MlpShape& sh);
 // Next-value reuse of the old-policy evaluation over a [T][row] rollout: where next_obs[i] is
 // bitwise obs[i + row], V(next_obs[i]) = values[i + row]; only the other samples get a critic
 // pass of their own, run by the eval kernel's waves from a wave-private LDS ring (no second
@@ -292,14 +291,17 @@ struct FusedAdam {
   int ls_n;
   int add_entropy_const;
 };
-// Fused minibatch kernels.  launch_mb runs the sample-split kernel (mbwave.hip: one wave per
-// SIMD, heads on VALU, up to 4 actions) where it applies and the feature-split two-team kernel
-// (mbstep.hip) otherwise -- more actions, the fused Adam tail, or DPPO_MB_LEGACY=1.  mb_grid
-// gives the workgroup count (= gradient slabs) of the kernel launch_mb will run.
+// Fused minibatch kernels.  Each kernel file exports its own *_grid (the workgroup count = gradient
+// slabs for a minibatch of m samples), *_lds_bytes and launch_*, and knows no other family; which
+// one runs is decided in dispatch.cpp (below).
+// Feature-split two-team kernel (mbstep.hip): any tuned shape, and the only one with the fused
+// Adam tail.
 size_t mb_lds_bytes(const MlpShape& sh);
-int mb_grid(const MlpShape& sh, int32_t m, bool fused = false);
+int mb_grid(int32_t m);
 int launch_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, int G,
               hipStream_t s, const FusedAdam* fused = nullptr);
+// Sample-split kernel (mbwave.hip: one wave per SIMD, heads on VALU) for the tuned shapes that
+// mbw_supported admits -- few actions, and no DPPO_MB_LEGACY=1.
 bool mbw_supported(const MlpShape& sh);
 int mbw_grid(int32_t m);
 size_t mbw_lds_bytes(const MlpShape& sh);
@@ -309,8 +311,6 @@ int launch_mbw(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, in
 // Wide kernel family (mbwide.hip): hidden 128 with D <= 128, hidden 64 with 32 < D <= 128,
 // A <= 16.  One workgroup of H/16 waves per CU loops over 32-sample tiles and writes one slab;
 // wide_grid gives the workgroup count for a minibatch of m samples (at least two tiles each).
-bool tuned_shape(const MlpShape& sh);
-bool wide_shape(const MlpShape& sh);
 size_t wide_lds_bytes(const MlpShape& sh);
 int wide_tile();
 int wide_grid(const MlpShape& sh, int32_t m);
@@ -322,27 +322,47 @@ int launch_wide_eval(const MlpShape& sh, const ParamOffsets& po, const float* pa
 // pack_kernel's records without its LDS tile (which outgrows a CU past D = 32); mean_std = the
 // finalised advantage statistics (launch_stats_finalize)
 int launch_wide_pack(const PackArgs& a, const float* mean_std, hipStream_t s);
-// Shape-class dispatch: the tuned launchers above for tuned shapes, untouched; the wide family
-// otherwise.  capi.cpp calls only these.
-size_t fused_mb_lds_bytes(const MlpShape& sh);
-size_t fused_eval_lds_bytes(const MlpShape& sh);
-int fused_mb_grid(const MlpShape& sh, int32_t m, bool fused = false);
-int launch_fused_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, int G,
-                    hipStream_t s, const FusedAdam* fused = nullptr);
+// Kernel-family dispatch (dispatch.cpp): the one place that says which minibatch kernel runs.
+// The shape class is fixed per handle (numbered as dppo_fused_plan reports it); within the tuned
+// class the kernel also depends on whether the caller wants the fused Adam tail.  capi.cpp
+// launches minibatch and evaluation kernels only through these.
+enum ShapeClass : int32_t { kShapeNone = 0, kShapeTuned = 1, kShapeWide = 2 };
+enum class MbKernel { None, Split /*mbwave.hip*/, Team /*mbstep.hip*/, Wide /*mbwide.hip*/ };
+bool tuned_shape(const MlpShape& sh);  // hidden 64, D <= 32, A <= 16
+bool wide_shape(const MlpShape& sh);
+MbKernel pick_mb_kernel(const MlpShape& sh, bool fused_tail);
+int fused_mb_grid(MbKernel k, const MlpShape& sh, int32_t m);
+int launch_fused_mb(MbKernel k, const MlpShape& sh, const ParamOffsets& po, const GradArgs& a,
+                    int G, hipStream_t s, const FusedAdam* fused = nullptr);
 int launch_fused_eval(const MlpShape& sh, const ParamOffsets& po, const float* params,
                       const float* obs, const void* actions, const float* next_obs, float* logp,
                       float* values, float* next_values, int64_t n, hipStream_t s,
                       EvalReuse* reuse = nullptr);
 
+// One optimiser step as the host describes it: capi.cpp builds both structs, the launchers unpack
+// them into the kernels' parameter lists (FusedAdam included).
+// LogStdTerm: d(-beta * mean H)/d log_std = -beta per action dimension of the continuous head, a
+// constant the per-sample kernels do not see; whoever reduces the slabs adds it, once over all ranks.
+struct LogStdTerm {
+  int64_t ls_off;
+  int ls_n;
+  float ent_coef;
+  int add_entropy_const;
+};
+// clip_grad_norm_ + Adam with the step's bias corrections folded in, and the trace row's scaling.
+struct AdamStep {
+  float *params, *m, *v;  // updated in place
+  float max_norm, neg_step_size, bc2_sqrt, beta1, beta2, eps;
+  float* trace;           // or null: [5] {loss, l_pi, l_v, H, norm} of this minibatch
+  float inv_m, vf, ent;
+};
+
 // Optimiser kernels: optim.hip.
 int slab_reduce_blocks(int64_t p_total);
 int launch_slab_reduce(const float* slabs, int G, int64_t slab_stride, int64_t p_total,
-                       float* grad, double* sq_part, int64_t ls_off, int ls_n, float ent_coef,
-                       int add_entropy_const, hipStream_t s);
-int launch_clip_adam_traced(float* params, float* grad, float* m, float* v, int64_t n,
-                            const double* sq_part, int n_sq, float max_norm, float neg_step_size,
-                            float bc2_sqrt, float beta1, float beta2, float eps, float* out_norm,
-                            float* trace, float inv_m, float vf, float ent, hipStream_t s);
+                       float* grad, double* sq_part, const LogStdTerm& ls, hipStream_t s);
+int launch_clip_adam_traced(const AdamStep& st, float* grad, int64_t n, const double* sq_part,
+                            int n_sq, float* out_norm, hipStream_t s);
 // slab reduce + clip + Adam fused (single device): `tags` = reduce_adam_tag_words(p_total)
 // 64-bit words zeroed once; launch number `epoch` (1, 2, ...) publishes and waits for words
 // tagged `epoch`.  On a wait timeout the blocks leave their parameters untouched and set *err.
@@ -350,12 +370,9 @@ struct PeerArgs;
 // `peer` (may be null): sum each block's gradient slice over the ranks of a peer exchange before
 // the norm (peer.hip; src / dst / n unused, seq = this exchange's number)
 int launch_reduce_adam(const float* slabs, int G, int64_t slab_stride, int64_t p_total, float* grad,
-                       unsigned long long* tags, int64_t ls_off, int ls_n, float ent_coef,
-                       int add_entropy_const, unsigned epoch, float* params,
-                       float* m, float* v, float max_norm, float neg_step_size, float bc2_sqrt,
-                       float beta1, float beta2, float eps, float* trace, float inv_m, float vf,
-                       float ent, unsigned* err, unsigned long long timeout_ticks, hipStream_t s,
-                       const PeerArgs* peer = nullptr);
+                       unsigned long long* tags, const LogStdTerm& ls, unsigned epoch,
+                       const AdamStep& st, unsigned* err, unsigned long long timeout_ticks,
+                       hipStream_t s, const PeerArgs* peer = nullptr);
 // Workgroups of reduce_adam_kernel that fit on the device at once (occupancy x CUs; 0 when the
 // layout has more tagged words than the kernel's polling wave holds).
 int reduce_adam_capacity(int device, int64_t p_total);
@@ -365,9 +382,6 @@ int reduce_adam_tag_words(int64_t p_total);
 // `lds_bytes` of LDS each meet in one grid_fanin on `ctr` (zeroed by the caller, epoch 1).
 int launch_fanin_probe(int blocks, int lds_bytes, unsigned* ctr, unsigned* err,
                        unsigned long long timeout_ticks, hipStream_t s);
-int launch_clip_adam(float* params, float* grad, float* m, float* v, int64_t n, float max_norm,
-                     float neg_step_size, float bc2_sqrt, float beta1, float beta2, float eps,
-                     float* out_norm, hipStream_t s);
 // out[i] = src[0][i] + src[1][i] + ... + src[n-1][i] in rank order (f32 or f64 when `f64`); the
 // device-local stand-in for the RCCL sum of a single-device loopback group (capi.cpp)
 constexpr int kMaxLoopRanks = 8;

@@ -755,8 +755,8 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
                            hp->ppo_clip, hp->value_loss_weight, hp->entropy_beta, h->sc, h->slabs,
                            h->slab_stride, h->layout.total, s);
   if (rc != DPPO_OK) return rc;
-  return launch_slab_reduce(h->slabs, h->G, h->slab_stride, h->layout.total, grad, h->sq_part, -1,
-                            0, 0.0f, 0, s);
+  return launch_slab_reduce(h->slabs, h->G, h->slab_stride, h->layout.total, grad, h->sq_part,
+                            LogStdTerm{-1, 0, 0.0f, 0}, s);
 }
 
 }  // extern "C"

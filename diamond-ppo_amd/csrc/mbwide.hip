@@ -34,7 +34,6 @@ namespace {
 
 constexpr int S = 32;     // samples per tile
 constexpr int SDO = 36;   // stride of the head-delta image: [0,16) dout, [16,32) d log_std terms
-constexpr int kMaxD = 128;
 constexpr int kMinTiles = 2;  // tiles per workgroup before another workgroup (slab) is added
 constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
 constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;
@@ -675,13 +674,6 @@ void raise_wide_lds() {
 
 }  // namespace
 
-bool tuned_shape(const MlpShape& sh) { return sh.H == 64 && sh.D <= 32 && sh.A <= 16; }
-
-bool wide_shape(const MlpShape& sh) {
-  if (sh.A < 1 || sh.A > 16 || sh.D < 1 || sh.D > kMaxD) return false;
-  return sh.H == 128 || (sh.H == 64 && sh.D > 32);
-}
-
 size_t wide_lds_bytes(const MlpShape& sh) {
   return (size_t)make_wlds(sh.H, (sh.D + 15) / 16 * 16).total * sizeof(float);
 }
@@ -779,40 +771,6 @@ int launch_wide_pack(const PackArgs& a, const float* mean_std, hipStream_t s) {
   DPPO_LAUNCH(wide_pack_kernel, dim3((unsigned)g), dim3(256), 0, s, w);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
-}
-
-// ---- dispatch between the tuned family (mbwave.hip / mbstep.hip / mlp.hip) and this one
-size_t fused_mb_lds_bytes(const MlpShape& sh) {
-  return tuned_shape(sh) ? mb_lds_bytes(sh) : wide_shape(sh) ? wide_lds_bytes(sh) : 0;
-}
-
-size_t fused_eval_lds_bytes(const MlpShape& sh) {
-  return tuned_shape(sh) ? mlp_lds_bytes_eval(sh) : wide_shape(sh) ? wide_lds_bytes(sh) : 0;
-}
-
-int fused_mb_grid(const MlpShape& sh, int32_t m, bool fused) {
-  // (shapes of neither class launch nothing: their handles keep the tuned sizing they had)
-  return wide_shape(sh) && !tuned_shape(sh) ? wide_grid(sh, m) : mb_grid(sh, m, fused);
-}
-
-int launch_fused_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, int G,
-                    hipStream_t s, const FusedAdam* fused) {
-  if (tuned_shape(sh)) return launch_mb(sh, po, a, G, s, fused);
-  if (fused) {
-    set_error("the fused Adam tail exists only for the tuned shape class");
-    return DPPO_EUNSUPPORTED;
-  }
-  return launch_wide_mb(sh, po, a, G, s);
-}
-
-int launch_fused_eval(const MlpShape& sh, const ParamOffsets& po, const float* params,
-                      const float* obs, const void* actions, const float* next_obs, float* logp,
-                      float* values, float* next_values, int64_t n, hipStream_t s,
-                      EvalReuse* reuse) {
-  if (tuned_shape(sh))
-    return launch_eval(sh, po, params, obs, actions, next_obs, logp, values, next_values, n, s,
-                       reuse);
-  return launch_wide_eval(sh, po, params, obs, actions, next_obs, logp, values, next_values, n, s);
 }
 
 }  // namespace dppo

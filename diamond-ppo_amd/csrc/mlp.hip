@@ -740,11 +740,6 @@ int cu_count() {
 
 }  // namespace
 
-size_t mlp_lds_bytes_eval(const MlpShape& sh) {
-  const LdsLayout L = make_layout(sh);
-  return (size_t)L.total * sizeof(float);
-}
-
 int launch_eval(const MlpShape& sh, const ParamOffsets& po, const float* params, const float* obs,
                 const void* actions, const float* next_obs, float* logp, float* values,
                 float* next_values, int64_t n, hipStream_t s, EvalReuse* reuse) {

@@ -400,36 +400,30 @@ int launch_rank_sum(const RankPtrs& src, int n, void* out, int64_t count, bool f
 int slab_reduce_blocks(int64_t p_total) { return (int)((p_total + 8 + kRedParams - 1) / kRedParams); }
 
 int launch_slab_reduce(const float* slabs, int G, int64_t slab_stride, int64_t p_total,
-                       float* grad, double* sq_part, int64_t ls_off, int ls_n, float ent_coef,
-                       int add_entropy_const, hipStream_t s) {
+                       float* grad, double* sq_part, const LogStdTerm& ls, hipStream_t s) {
   DPPO_LAUNCH(slab_reduce_kernel, dim3(slab_reduce_blocks(p_total)), dim3(kRedThreads), 0, s,
-                     slabs, G, slab_stride, p_total, grad, sq_part, ls_off, ls_n, ent_coef,
-                     add_entropy_const);
+                     slabs, G, slab_stride, p_total, grad, sq_part, ls.ls_off, ls.ls_n, ls.ent_coef,
+                     ls.add_entropy_const);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }
 
-int launch_clip_adam_traced(float* params, float* grad, float* m, float* v, int64_t n,
-                            const double* sq_part, int n_sq, float max_norm, float neg_step_size,
-                            float bc2_sqrt, float beta1, float beta2, float eps, float* out_norm,
-                            float* trace, float inv_m, float vf, float ent, hipStream_t s) {
+int launch_clip_adam_traced(const AdamStep& st, float* grad, int64_t n, const double* sq_part,
+                            int n_sq, float* out_norm, hipStream_t s) {
   int64_t g = (n + 255) / 256;
   if (g > 256) g = 256;
   if (g < 1) g = 1;
-  DPPO_LAUNCH(clip_adam_kernel, dim3((unsigned)g), dim3(256), 0, s, params, grad, m, v, n,
-                     sq_part, n_sq, max_norm, neg_step_size, bc2_sqrt, beta1, beta2, eps,
-                     out_norm, trace, inv_m, vf, ent);
+  DPPO_LAUNCH(clip_adam_kernel, dim3((unsigned)g), dim3(256), 0, s, st.params, grad, st.m, st.v, n,
+                     sq_part, n_sq, st.max_norm, st.neg_step_size, st.bc2_sqrt, st.beta1, st.beta2,
+                     st.eps, out_norm, st.trace, st.inv_m, st.vf, st.ent);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }
 
 int launch_reduce_adam(const float* slabs, int G, int64_t slab_stride, int64_t p_total, float* grad,
-                       unsigned long long* tags, int64_t ls_off, int ls_n, float ent_coef,
-                       int add_entropy_const, unsigned epoch, float* params,
-                       float* m, float* v, float max_norm, float neg_step_size, float bc2_sqrt,
-                       float beta1, float beta2, float eps, float* trace, float inv_m, float vf,
-                       float ent, unsigned* err, unsigned long long timeout_ticks, hipStream_t s,
-                       const PeerArgs* peer) {
+                       unsigned long long* tags, const LogStdTerm& ls, unsigned epoch,
+                       const AdamStep& st, unsigned* err, unsigned long long timeout_ticks,
+                       hipStream_t s, const PeerArgs* peer) {
   PeerArgs pl{};
   if (peer) {
     pl = *peer;
@@ -440,9 +434,10 @@ int launch_reduce_adam(const float* slabs, int G, int64_t slab_stride, int64_t p
     }
   }
   DPPO_LAUNCH(reduce_adam_kernel, dim3(reduce_adam_blocks(p_total)), dim3(kRedThreads), 0, s, slabs, G,
-              slab_stride, p_total, grad, tags, ls_off, ls_n, ent_coef, add_entropy_const,
-              epoch, params, m, v, max_norm, neg_step_size, bc2_sqrt, beta1, beta2, eps,
-              trace, inv_m, vf, ent, err, timeout_ticks, pl);
+              slab_stride, p_total, grad, tags, ls.ls_off, ls.ls_n, ls.ent_coef,
+              ls.add_entropy_const, epoch, st.params, st.m, st.v, st.max_norm, st.neg_step_size,
+              st.bc2_sqrt, st.beta1, st.beta2, st.eps, st.trace, st.inv_m, st.vf, st.ent, err,
+              timeout_ticks, pl);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }
@@ -473,13 +468,6 @@ int launch_fanin_probe(int blocks, int lds_bytes, unsigned* ctr, unsigned* err,
               err, timeout_ticks);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
-}
-
-int launch_clip_adam(float* params, float* grad, float* m, float* v, int64_t n, float max_norm,
-                     float neg_step_size, float bc2_sqrt, float beta1, float beta2, float eps,
-                     float* out_norm, hipStream_t s) {
-  return launch_clip_adam_traced(params, grad, m, v, n, nullptr, 0, max_norm, neg_step_size,
-                                 bc2_sqrt, beta1, beta2, eps, out_norm, nullptr, 0.f, 0.f, 0.f, s);
 }
 
 }  // namespace dppo

@@ -1,6 +1,6 @@
 """GPU parity of the minibatch kernels in their PRODUCTION configuration.
 
-Two kernels compute a minibatch gradient (csrc/common.h launch_mb):
+Two kernels compute a minibatch gradient (csrc/dispatch.cpp pick_mb_kernel):
 * the sample-split kernel (csrc/mbwave.hip; <= 4 actions, <= 8 discrete on <= 16 inputs, or
   HalfCheetah's 5-6 Gaussian actions on exactly 17 inputs -- the X1 instantiation):
   G = min(ceil(m/64), 256) workgroups of 4 waves, each wave running ceil(ceil(m/16) / 4G)

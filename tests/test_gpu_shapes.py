@@ -1,7 +1,7 @@
 """GPU parity of the minibatch gradient over a seeded sweep of network shapes.
 
 Both minibatch kernels (csrc/mbwave.hip sample-split, csrc/mbstep.hip two-team; the dispatch is
-csrc/common.h launch_mb / mbwave.hip mbw_supported) are instantiated per (action rows, Gaussian
+csrc/dispatch.cpp pick_mb_kernel / mbwave.hip mbw_supported) are instantiated per (action rows, Gaussian
 head, input width) class.  This sweep draws 24 shapes from a fixed seed -- observation widths
 1..32 (one or two 16-input column blocks, layer-1 k-steps 1..8), 1..8 actions, categorical and
 Gaussian heads, minibatch sizes that leave partial 16-sample groups and idle waves / workgroups --
