@@ -470,6 +470,21 @@ int launch_gru_grad(const GruOffsets& po, const float* params, const dppo_gru_ba
                     int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
                     float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s);
 
+// The GRU kernels' gate non-linearities (gru.hip learn, gruact.hip rollout: the same bits)
+__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float tanh_acc(float x) {
+  // 1 - 2 / (e^{2x} + 1): saturates cleanly, ~1e-7 absolute
+  return 1.0f - 2.0f / (__expf(2.0f * x) + 1.0f);
+}
+
+// RecurrentPPO rollout step (gruact.hip): one GRU step per env from hx, then either both heads,
+// the Categorical draw and its log-prob (launch_gru_act; logits optional) or the critic head
+// alone (launch_gru_value; dones optional, the new hidden state discarded).  n > 0.
+int launch_gru_act(const GruOffsets& po, const float* params, const dppo_gru_step& st, int64_t n,
+                   int D, int A, uint64_t seed, uint64_t counter, hipStream_t s);
+int launch_gru_value(const GruOffsets& po, const float* params, const float* obs, const float* hx,
+                     const uint8_t* dones, int64_t n, int D, float* values, hipStream_t s);
+
 // Fisher-Yates resolution (shuffle.hip): perms[c][n] from swap targets[c][n]; scratch of
 // scratch_ints >= 3 * count * n int32 (perm_scratch_ints: the size at which the partitioned
 // buckets run fused).

@@ -24,6 +24,7 @@
 //     (v_mfma_f32_16x16x4_f32, k = sample) in a fixed order; bias sums on VALU; one slab per
 //     workgroup (optim.hip's slab reduction sums them in a fixed order: bit-reproducible).
 #include <cstring>
+#include <vector>
 
 #include "common.h"
 
@@ -75,12 +76,6 @@ __host__ __device__ constexpr GruLds gru_lds(int D) {
   L.red = o; o += 4 * kThr;
   L.total = o;
   return L;
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_acc(float x) {
-  // 1 - 2 / (e^{2x} + 1): saturates cleanly, ~1e-7 absolute
-  return 1.0f - 2.0f / (__expf(2.0f * x) + 1.0f);
 }
 
 // Sum over k = samples of A[s][m] B[s][n] for one 16 x 16 output tile: rows mt*16.., cols nt*16..
@@ -599,6 +594,15 @@ struct dppo_gru_handle {
   float* wmask = nullptr;
   float* slabs = nullptr;
   double* sq_part = nullptr;
+  // optional timing of the rollout kernels (dppo_gru_set_timing): event pairs per launch
+  bool timing = false;
+  std::vector<hipEvent_t> pool;
+  size_t pool_used = 0;
+  struct Rec {
+    int cls;
+    hipEvent_t a, b;
+  };
+  std::vector<Rec> recs;
 };
 
 namespace {
@@ -641,6 +645,30 @@ void gru_layout(const dppo_gru_dims* d, dppo_layout* L) {
   L->n_real = real;
 }
 
+// Hands the next launch of this thread an event pair of its own when the handle's timing is on
+// (g_launch_timing, common.h); otherwise does nothing.
+struct GruTimed {
+  dppo_gru_handle* h;
+  GruTimed(dppo_gru_handle* h_, int cls) : h(h_) {
+    if (!h->timing) return;
+    while (h->pool.size() < h->pool_used + 2) {
+      hipEvent_t e = nullptr;
+      if (hipEventCreate(&e) != hipSuccess) return;
+      h->pool.push_back(e);
+    }
+    const hipEvent_t a = h->pool[h->pool_used], b = h->pool[h->pool_used + 1];
+    h->pool_used += 2;
+    g_launch_timing.start = a;
+    g_launch_timing.stop = b;
+    h->recs.push_back({cls, a, b});
+  }
+  ~GruTimed() {
+    if (!g_launch_timing.stop) return;
+    if (g_launch_timing.start) h->recs.pop_back();  // nothing was launched
+    g_launch_timing = LaunchTiming{};
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -664,6 +692,7 @@ void dppo_gru_destroy(dppo_gru_handle* h) {
   (void)hipFree(h->wmask);
   (void)hipFree(h->slabs);
   (void)hipFree(h->sq_part);
+  for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   delete h;
 }
 
@@ -757,6 +786,70 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
   if (rc != DPPO_OK) return rc;
   return launch_slab_reduce(h->slabs, h->G, h->slab_stride, h->layout.total, grad, h->sq_part,
                             LogStdTerm{-1, 0, 0.0f, 0}, s);
+}
+
+int dppo_gru_act_f32(dppo_gru_handle* h, const float* params, const dppo_gru_step* step,
+                     int64_t n, uint64_t seed, uint64_t counter, void* stream) {
+  if (!h || !params || !step || n < 0 || !step->obs || !step->prev_dones || !step->hx ||
+      !step->hx_out || !step->actions || !step->log_probs || !step->values ||
+      step->hx_out == step->hx || (uintptr_t)params % 16 != 0) {
+    set_error("invalid argument to dppo_gru_act_f32 (NULL pointer, n < 0, hx_out == hx or "
+              "params not 16-byte aligned)");
+    return DPPO_EINVAL;
+  }
+  if (n == 0) return DPPO_OK;
+  DPPO_HIP_CHECK(hipSetDevice(h->device));
+  GruTimed timed(h, 0);
+  return launch_gru_act(h->po, params, *step, n, h->dims.obs_dim, h->dims.act_dim, seed, counter,
+                        (hipStream_t)stream);
+}
+
+int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs,
+                       const float* hx, const uint8_t* dones, int64_t n, float* values,
+                       void* stream) {
+  if (!h || !params || !obs || !hx || !values || n < 0 || (uintptr_t)params % 16 != 0) {
+    set_error("invalid argument to dppo_gru_value_f32 (NULL pointer, n < 0 or params not "
+              "16-byte aligned)");
+    return DPPO_EINVAL;
+  }
+  if (n == 0) return DPPO_OK;
+  DPPO_HIP_CHECK(hipSetDevice(h->device));
+  GruTimed timed(h, 1);
+  return launch_gru_value(h->po, params, obs, hx, dones, n, h->dims.obs_dim, values,
+                          (hipStream_t)stream);
+}
+
+int dppo_gru_set_timing(dppo_gru_handle* h, int32_t enable) {
+  if (!h) {
+    set_error("null handle");
+    return DPPO_EINVAL;
+  }
+  DPPO_HIP_CHECK(hipSetDevice(h->device));
+  DPPO_HIP_CHECK(hipDeviceSynchronize());
+  h->timing = enable != 0;
+  h->recs.clear();
+  h->pool_used = 0;
+  return DPPO_OK;
+}
+
+int dppo_gru_get_timing(dppo_gru_handle* h, double* ms_sum, int64_t* counts) {
+  if (!h || !ms_sum || !counts) {
+    set_error("null argument to dppo_gru_get_timing");
+    return DPPO_EINVAL;
+  }
+  DPPO_HIP_CHECK(hipSetDevice(h->device));
+  for (int k = 0; k < DPPO_GRU_TIMING_CLASSES; ++k) {
+    ms_sum[k] = 0.0;
+    counts[k] = 0;
+  }
+  for (const auto& r : h->recs) {
+    DPPO_HIP_CHECK(hipEventSynchronize(r.b));
+    float ms = 0.f;
+    DPPO_HIP_CHECK(hipEventElapsedTime(&ms, r.a, r.b));
+    ms_sum[r.cls] += ms;
+    counts[r.cls] += 1;
+  }
+  return DPPO_OK;
 }
 
 }  // extern "C"

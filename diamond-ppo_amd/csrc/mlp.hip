@@ -21,6 +21,7 @@
 // blocks live (h1 -> h2 -> critic -> value -> actor -> heads), under the 128-VGPR budget of four
 // waves per SIMD.
 #include "common.h"
+#include "philox.h"
 
 namespace dppo {
 namespace {
@@ -519,30 +520,7 @@ __global__ __launch_bounds__(kThreads, 4) void eval_kernel(KArgs a) {
 // actor forward, then Categorical(logits).sample() or Normal(mean, exp(log_std)).sample() on the
 // lane that holds the sample.  Randomness: Philox4x32-10 keyed by `seed`, counter (sample index,
 // call counter) -- a deterministic stream of its own (the reference draws from torch's generator:
-// same distribution, not the same draws).
-__device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) {
-  return (uint32_t)(((uint64_t)a * b) >> 32);
-}
-
-__device__ __forceinline__ void philox4x32(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = mulhi32(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = mulhi32(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    c[0] = hi1 ^ c[1] ^ k0;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ k1;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// u32 -> uniform in (0, 1): 24 random bits, centred in their interval (never 0 or 1)
-__device__ __forceinline__ float u01(uint32_t x) {
-  return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
-}
-
+// same distribution, not the same draws).  The generator itself lives in philox.h.
 struct ActArgs {
   LdsLayout L;
   ParamOffsets po;

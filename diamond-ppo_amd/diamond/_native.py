@@ -37,9 +37,11 @@ EXPORTED = [
     "dppo_peer_export", "dppo_peer_open", "dppo_peer_close", "dppo_peer_allreduce", "dppo_peer_info",
     "dppo_peer_selftest",
     "dppo_gru_param_layout", "dppo_gru_create", "dppo_gru_destroy", "dppo_gru_minibatch_grad_f32",
+    "dppo_gru_act_f32", "dppo_gru_value_f32", "dppo_gru_set_timing", "dppo_gru_get_timing",
 ]
 TIMING_CLASSES = ["eval", "gae", "adv_stats", "pack", "grad", "slab_reduce", "clip_adam",
                   "allreduce", "perm", "reduce_adam", "gae_probe"]
+GRU_TIMING_CLASSES = ["act", "value"]  # dppo_gru_get_timing
 
 
 class Dims(ctypes.Structure):
@@ -78,6 +80,14 @@ class GruBatch(ctypes.Structure):
                 ("old_log_probs", ctypes.c_void_p), ("advantages", ctypes.c_void_p),
                 ("returns", ctypes.c_void_p), ("prev_dones", ctypes.c_void_p),
                 ("hx0", ctypes.c_void_p)]
+
+
+class GruStep(ctypes.Structure):
+    """dppo_gru_step: device pointers of one rollout step (logits optional)."""
+    _fields_ = [("obs", ctypes.c_void_p), ("prev_dones", ctypes.c_void_p),
+                ("hx", ctypes.c_void_p), ("hx_out", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("log_probs", ctypes.c_void_p),
+                ("values", ctypes.c_void_p), ("logits", ctypes.c_void_p)]
 
 
 class Rollout(ctypes.Structure):
@@ -166,6 +176,11 @@ def load():
         "dppo_gru_destroy": (None, [vp]),
         "dppo_gru_minibatch_grad_f32": (ctypes.c_int, [vp, vp, P(GruBatch), vp, i32, i32,
                                                        P(HParams), vp, vp]),
+        "dppo_gru_act_f32": (ctypes.c_int, [vp, vp, P(GruStep), i64, ctypes.c_uint64,
+                                            ctypes.c_uint64, vp]),
+        "dppo_gru_value_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, vp, vp]),
+        "dppo_gru_set_timing": (ctypes.c_int, [vp, i32]),
+        "dppo_gru_get_timing": (ctypes.c_int, [vp, vp, vp]),
         "dppo_set_timing": (ctypes.c_int, [vp, i32]),
         "dppo_get_timing": (ctypes.c_int, [vp, vp, vp]),
     }
@@ -459,7 +474,8 @@ class Handle:
 
 
 class GruHandle:
-    """Owns one dppo_gru_handle (RecurrentPPO's fused minibatch-gradient workspace)."""
+    """Owns one dppo_gru_handle (RecurrentPPO's fused minibatch-gradient workspace; the
+    rollout kernels dppo_gru_act_f32 / dppo_gru_value_f32 take it for its shape and layout)."""
 
     def __init__(self, device_index: int, dims: GruDims):
         self.lib = load()
@@ -471,6 +487,18 @@ class GruHandle:
         self.layout = Layout()
         check(self.lib.dppo_gru_param_layout(ctypes.byref(dims), ctypes.byref(self.layout)),
               "dppo_gru_param_layout")
+
+    def set_timing(self, enable: bool):
+        check(self.lib.dppo_gru_set_timing(self.h, int(bool(enable))), "dppo_gru_set_timing")
+
+    def timing(self) -> dict:
+        """{"act" | "value": (total_ms, launches)} of the rollout kernels since set_timing(True)
+        (synchronises)."""
+        ms = np.zeros(len(GRU_TIMING_CLASSES), np.float64)
+        cnt = np.zeros(len(GRU_TIMING_CLASSES), np.int64)
+        check(self.lib.dppo_gru_get_timing(self.h, ms.ctypes.data, cnt.ctypes.data),
+              "dppo_gru_get_timing")
+        return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(GRU_TIMING_CLASSES)}
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

@@ -7,7 +7,9 @@ semantics: per-timestep GRU with the hidden state reset where ``dones[t]`` (:82-
 log-probs / values / next-values cached during rollout (:219-243), and ``learn`` recomputing the
 full [T, N] sequence from the stored initial ``hx`` for every minibatch (:337-341).  The network
 runs under torch autograd on the GPU; GAE, advantage normalisation and clip + Adam run in the
-gfx950 kernels.  No oracle pins this path beyond the shared GAE (reference broken).
+gfx950 kernels.  No oracle pins this path beyond the shared GAE (reference broken).  For the
+default network, learn()'s minibatches (``fused_gru``) and, when switched on, rollout()'s env steps
+(``fused_rollout``) run as fused HIP kernels instead.
 
 Data parallelism (torchrun, one process per GPU): each rank owns its own envs (seeded
 ``seed + rank * num_envs``) and permutes its own samples (``np.random`` seeded ``seed + rank``);
@@ -124,6 +126,11 @@ class RecurrentPPO:
     # (dppo_gru_minibatch_grad_f32) for the default network at supported shapes; False (or any
     # other network_cls) runs the network under torch autograd on the GPU
     fused_gru = True
+    # rollout() runs each env step's policy forward, Categorical draw and log-prob as one fused HIP
+    # launch (dppo_gru_act_f32) and V(next_obs) as another (dppo_gru_value_f32), under the same
+    # conditions as fused_gru.  Off by default: the actions then come from torch's generator, as
+    # before; the fused path draws from its own Philox stream (same distribution, other draws)
+    fused_rollout = False
 
     def __init__(self, env_fn: Callable[[], Any], cfg: RecurrentPPOConfig = RecurrentPPOConfig(),
                  network_cls: Any = RecurrentActorCriticNetwork, envs=None) -> None:
@@ -161,6 +168,11 @@ class RecurrentPPO:
                                                   enumerate(self.flat.offsets)):
                 raise RuntimeError("RecurrentActorCriticNetwork layout differs from libdppo's")
         self.last_losses = None
+        # the fused rollout's Philox key (mixed as _AgentBase._act_seed) and call counter
+        base_seed = cfg.seed if cfg.seed is not None else torch.initial_seed()
+        self._act_seed = (int(base_seed) * 0x9E3779B97F4A7C15 + rank) & (2 ** 64 - 1)
+        self._act_counter = 0
+        self._rollout_staging = None
         if not getattr(cfg, "gae_bitexact", True):
             self.handle.set_gae_mode(N.GAE_AFFINE)
         if world > 1:   # replicate rank 0's initial weights (identical seeds: a no-op in practice)
@@ -178,6 +190,8 @@ class RecurrentPPO:
 
     def rollout(self):
         """recurrent_ppo.py:205-263 with tensor-safe hidden-state handling."""
+        if self.fused_rollout and self.gru is not None:
+            return self._rollout_fused()
         experience = []
         observations, hx, prev_dones = self.current_observations, self.current_hx, self.prev_dones
         for _ in range(self.cfg.rollout_steps):
@@ -203,6 +217,70 @@ class RecurrentPPO:
                 self.ticker.tick(rewards, dones)
         self.current_observations, self.current_hx, self.prev_dones = observations, hx, prev_dones
         return experience
+
+    def _rollout_fused(self):
+        """rollout() on the fused kernels.  Per env step: the observations and prev_dones go up
+        through pinned staging, one dppo_gru_act_f32 launch (recurrent_ppo.py:214-224), the int32
+        actions come down (the step's only synchronisation), the envs step, next_observations go
+        up and one dppo_gru_value_f32 launch follows from the step's new hidden state (:226-232)
+        without a synchronisation.  Everything lands in device buffers allocated per call, so a
+        returned experience outlives the next rollout; its rows are views of them, in the torch
+        path's layout."""
+        cfg, dev, lib = self.cfg, self.device, self.gru.lib
+        T, Nn, G = cfg.rollout_steps, cfg.num_envs, cfg.gru_hidden_dim
+        D, A = self.gru.dims.obs_dim, self.gru.dims.act_dim
+        st = self._rollout_staging
+        if st is None:
+            pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()
+            st = self._rollout_staging = {
+                "obs": pin((Nn, D), torch.float32), "dones": pin((Nn,), torch.bool),
+                "nobs": pin((Nn, D), torch.float32), "act": pin((Nn,), torch.int32),
+                "nobs_d": torch.empty((Nn, D), dtype=torch.float32, device=dev)}
+            for k in ("obs", "dones", "nobs", "act"):
+                st[k + "_np"] = st[k].numpy()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        obs_d, hx_d = f32(T, Nn, D), f32(T + 1, 1, Nn, G)
+        lp_d, v_d, nv_d = f32(T, Nn), f32(T, Nn), f32(T, Nn)
+        pd_d = torch.empty((T, Nn), dtype=torch.bool, device=dev)
+        act_d = torch.empty((T, Nn), dtype=torch.int32, device=dev)
+        hx_d[0].copy_(self.current_hx.reshape(1, Nn, G))
+        stream = torch.cuda.current_stream(dev)
+        params = self.flat.flat.data_ptr()
+        host = []
+        observations, prev_dones = self.current_observations, self.prev_dones
+        for t in range(T):
+            st["obs_np"][...] = np.asarray(observations, dtype=np.float32).reshape(Nn, D)
+            st["dones_np"][...] = prev_dones
+            obs_d[t].copy_(st["obs"], non_blocking=True)
+            pd_d[t].copy_(st["dones"], non_blocking=True)
+            step = N.GruStep(obs_d[t].data_ptr(), pd_d[t].data_ptr(), hx_d[t].data_ptr(),
+                             hx_d[t + 1].data_ptr(), act_d[t].data_ptr(), lp_d[t].data_ptr(),
+                             v_d[t].data_ptr(), None)
+            N.check(lib.dppo_gru_act_f32(self.gru.h, params, ctypes.byref(step), Nn,
+                                         self._act_seed, self._act_counter, stream.cuda_stream),
+                    "dppo_gru_act_f32")
+            self._act_counter += 1
+            st["act"].copy_(act_d[t], non_blocking=True)
+            stream.synchronize()
+            next_observations, rewards, terms, truncs, infos = self.envs.step(
+                st["act_np"].astype(np.int64))
+            st["nobs_np"][...] = np.asarray(next_observations, dtype=np.float32).reshape(Nn, D)
+            st["nobs_d"].copy_(st["nobs"], non_blocking=True)
+            N.check(lib.dppo_gru_value_f32(self.gru.h, params, st["nobs_d"].data_ptr(),
+                                           hx_d[t + 1].data_ptr(), None, Nn, nv_d[t].data_ptr(),
+                                           stream.cuda_stream), "dppo_gru_value_f32")
+            host.append((rewards, terms, truncs))
+            dones = np.logical_or(terms, truncs)
+            observations, infos = (self.envs.reset(options={"reset_mask": dones})
+                                   if np.any(dones) else (next_observations, infos))
+            prev_dones = dones
+            if self.ticker is not None:
+                self.ticker.tick(rewards, dones)
+        act64 = act_d.to(torch.int64)
+        self.current_observations, self.prev_dones = observations, prev_dones
+        self.current_hx = hx_d[T]
+        return [[obs_d[t], act64[t], *host[t], pd_d[t], lp_d[t], v_d[t], nv_d[t], hx_d[t]]
+                for t in range(T)]
 
     def calculate_advantage(self, rewards, terminations, truncations, values, next_values):
         """Shared GAE (recurrent_ppo.py:265-299) on the gfx950 kernel."""

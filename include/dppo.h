@@ -464,6 +464,48 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
                                 int32_t m_total, const dppo_hparams* hp, float* grad,
                                 void* stream);
 
+/* One rollout step of n envs (recurrent_ppo.py:214-245), device pointers. */
+typedef struct dppo_gru_step {
+  const float* obs;          /* [n][D] */
+  const uint8_t* prev_dones; /* [n], hidden state zeroed before the step where set (:84) */
+  const float* hx;           /* [n][16] hidden state before the step */
+  float* hx_out;             /* [n][16] after the step; must not alias hx */
+  int32_t* actions;          /* [n] sampled action */
+  float* log_probs;          /* [n] log-prob of the sampled action */
+  float* values;             /* [n] */
+  float* logits;             /* optional [n][A], may be NULL */
+} dppo_gru_step;
+
+/* The rollout's policy step in one launch (replaces get_logits_values_and_hx + Categorical
+ * sample / log_prob, recurrent_ppo.py:214-224 with the network of :94-149 and the hidden reset of
+ * :82-87): base layer, one GRU step from step->hx, both heads, a Categorical draw by inverse CDF
+ * and its log-prob (accurate logf / expf: learn() divides by it).  Randomness as dppo_act_f32:
+ * Philox4x32-10 keyed by `seed`, counter (sample index, `counter`); advance `counter` once per
+ * call.  A sample's outputs depend only on its own inputs and the parameters: the same bits at
+ * any n and any position in the batch (the draw alone depends on the sample index).  n is free
+ * (not tied to dims.num_envs); n == 0 returns DPPO_OK without a launch.  params: the flat layout,
+ * 16-byte aligned.  Stream-ordered, allocates nothing. */
+int dppo_gru_act_f32(dppo_gru_handle* h, const float* params, const dppo_gru_step* step,
+                     int64_t n, uint64_t seed, uint64_t counter, void* stream);
+
+/* V(next_obs) after the step (replaces get_values, recurrent_ppo.py:226-232): base layer, one
+ * GRU step from hx [n][16] (zeroed first where dones is set; dones may be NULL) and the critic
+ * head -> values [n].  The new hidden state is discarded, as in the reference.  Stream-ordered,
+ * allocates nothing. */
+int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs,
+                       const float* hx, const uint8_t* dones /* may be NULL */, int64_t n,
+                       float* values, void* stream);
+
+/* Per-kernel timing of the two rollout kernels with HIP events (off by default; as
+ * dppo_set_timing, no reference counterpart): while enabled every dppo_gru_act_f32 /
+ * dppo_gru_value_f32 launch carries an event pair stamped with the kernel's own execution
+ * interval.  dppo_gru_set_timing synchronises the device and clears the records;
+ * dppo_gru_get_timing synchronises and returns summed milliseconds and launch counts,
+ * [0] = act, [1] = value. */
+#define DPPO_GRU_TIMING_CLASSES 2
+int dppo_gru_set_timing(dppo_gru_handle* h, int32_t enable);
+int dppo_gru_get_timing(dppo_gru_handle* h, double* ms_sum, int64_t* counts);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""Time RecurrentPPO.rollout() with the fused step kernels against the torch path.
+
+    python tools/bench_recurrent_rollout.py --out profiles/recurrent_rollout.json
+
+Stub env (tests/golden/gym_stub.py: NumPy draws, no simulation, so the host side of a step is as
+cheap as an env gets), T = 32, N in {32, 1024, 8192}, D = 8, A = 4.  Per N two agents with the
+same weights, `fused_rollout` on and off, run their rollouts alternately (whatever else loads the
+host hits both alike): `--warmup` untimed rollouts each, then `--rollouts` timed ones, every one
+bracketed by a device synchronisation and the host wall clock (a rollout is 2-100 ms).  Reported:
+the median ms per rollout() of each path with min / max, and torch / fused.
+
+In a separate pass (events on every launch slow the host) the library's timing mode
+(dppo_gru_set_timing) gives the two kernels' own execution time per launch.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "diamond-ppo_amd"), ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np
+import torch
+
+import diamond
+import gym_stub
+
+T, D, A = 32, 8, 4
+SIZES = [32, 1024, 8192]
+
+
+def make_agent(Nn, fused):
+    np.random.seed(0)
+    torch.manual_seed(0)
+    envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
+    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False)
+    agent = diamond.RecurrentPPO(None, cfg, envs=envs)
+    assert agent.gru is not None
+    agent.fused_rollout = fused
+    agent.current_observations, _ = agent.envs.reset(seed=1)
+    agent.prev_dones = np.zeros(Nn, dtype=bool)
+    agent.current_hx = torch.zeros(1, Nn, cfg.gru_hidden_dim, device=agent.device)
+    return agent
+
+
+def timed_rollout(agent):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    agent.rollout()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def run(Nn, warmup, rollouts, kernel_rollouts):
+    agents = {"fused": make_agent(Nn, True), "torch": make_agent(Nn, False)}
+    ms = {k: [] for k in agents}
+    for r in range(warmup + rollouts):
+        for k, agent in agents.items():
+            t = timed_rollout(agent)
+            if r >= warmup:
+                ms[k].append(t)
+    out = {"N": Nn, "T": T, "D": D, "A": A, "warmup": warmup, "rollouts": rollouts}
+    for k, v in ms.items():
+        out[k + "_ms_median"] = statistics.median(v)
+        out[k + "_ms_min"], out[k + "_ms_max"] = min(v), max(v)
+    out["torch_over_fused"] = out["torch_ms_median"] / out["fused_ms_median"]
+    out["fused_is_slower"] = out["torch_over_fused"] < 1.0
+    gru = agents["fused"].gru
+    gru.set_timing(True)
+    for _ in range(kernel_rollouts):
+        agents["fused"].rollout()
+    kt = gru.timing()
+    gru.set_timing(False)
+    for k, (total, launches) in kt.items():
+        out[f"{k}_kernel_us_per_launch"] = 1e3 * total / max(launches, 1)
+        out[f"{k}_kernel_launches"] = launches
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rollouts", type=int, default=20)
+    ap.add_argument("--kernel-rollouts", type=int, default=5)
+    a = ap.parse_args()
+    res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "sizes": []}
+    for Nn in SIZES:
+        r = run(Nn, a.warmup, a.rollouts, a.kernel_rollouts)
+        print(json.dumps(r), flush=True)
+        res["sizes"].append(r)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
