@@ -388,18 +388,6 @@ int require_mlp(const dppo_handle* h) {
   return DPPO_OK;
 }
 
-// Rollout sampling (act kernels) exists for the tuned class only.
-int require_tuned(const dppo_handle* h) {
-  DPPO_TRY(require_mlp(h));
-  if (h->cls != kShapeTuned) {
-    set_error("the fused actor kernels support hidden=64, obs_dim<=32, act_dim<=16 only "
-              "(got H=%d D=%d A=%d): sample wide shapes with the network itself",
-              h->dims.hidden, h->dims.obs_dim, h->dims.act_dim);
-    return DPPO_EUNSUPPORTED;
-  }
-  return DPPO_OK;
-}
-
 // Whether learn() takes the exchanging (multi-rank) sequence: an RCCL communicator of any size
 // -- a 1-rank one too, so the collective path (slab reduce -> ncclAllReduce -> clip + Adam, the
 // advantage-stat all-reduce) runs and is tested on a single GPU -- or a loopback group.
@@ -1211,9 +1199,9 @@ int dppo_act_f32(dppo_handle* h, const float* params, const float* obs, int64_t 
     set_error("invalid argument to dppo_act_f32");
     return DPPO_EINVAL;
   }
-  DPPO_TRY(require_tuned(h));
+  DPPO_TRY(require_mlp(h));
   DPPO_HIP_CHECK(hipSetDevice(h->device));
-  return launch_act(h->sh, h->po, params, obs, actions, n, seed, counter, S(stream));
+  return launch_fused_act(h->sh, h->po, params, obs, actions, n, seed, counter, S(stream));
 }
 
 int dppo_act_squash_f32(dppo_handle* h, const float* params, const float* obs, int64_t n,
@@ -1223,7 +1211,7 @@ int dppo_act_squash_f32(dppo_handle* h, const float* params, const float* obs, i
     set_error("invalid argument to dppo_act_squash_f32");
     return DPPO_EINVAL;
   }
-  DPPO_TRY(require_tuned(h));
+  DPPO_TRY(require_mlp(h));
   if (!h->dims.continuous) {
     set_error("dppo_act_squash_f32 needs a continuous (Box) action space");
     return DPPO_EINVAL;
@@ -1238,7 +1226,8 @@ int dppo_act_squash_f32(dppo_handle* h, const float* params, const float* obs, i
   }
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   const ActSquash sq{env_actions, low, high};
-  return launch_act(h->sh, h->po, params, obs, actions, n, seed, counter, S(stream), nullptr, &sq);
+  return launch_fused_act(h->sh, h->po, params, obs, actions, n, seed, counter, S(stream),
+                          nullptr, &sq);
 }
 
 int dppo_actor_forward_f32(dppo_handle* h, const float* params, const float* obs, int64_t n,
@@ -1247,9 +1236,9 @@ int dppo_actor_forward_f32(dppo_handle* h, const float* params, const float* obs
     set_error("invalid argument to dppo_actor_forward_f32");
     return DPPO_EINVAL;
   }
-  DPPO_TRY(require_tuned(h));
+  DPPO_TRY(require_mlp(h));
   DPPO_HIP_CHECK(hipSetDevice(h->device));
-  return launch_act(h->sh, h->po, params, obs, nullptr, n, 0, 0, S(stream), heads);
+  return launch_fused_act(h->sh, h->po, params, obs, nullptr, n, 0, 0, S(stream), heads);
 }
 
 int dppo_prepare_f32(dppo_handle* h, const dppo_rollout* rollout, const float* params,

@@ -319,13 +319,17 @@ int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a
 int launch_wide_eval(const MlpShape& sh, const ParamOffsets& po, const float* params,
                      const float* obs, const void* actions, const float* next_obs, float* logp,
                      float* values, float* next_values, int64_t n, hipStream_t s);
+// launch_act's arguments and outputs (same Philox stream), on wide_act_kernel
+int launch_wide_act(const MlpShape& sh, const ParamOffsets& po, const float* params,
+                    const float* obs, void* actions, int64_t n, uint64_t seed, uint64_t counter,
+                    hipStream_t s, float* heads = nullptr, const ActSquash* squash = nullptr);
 // pack_kernel's records without its LDS tile (which outgrows a CU past D = 32); mean_std = the
 // finalised advantage statistics (launch_stats_finalize)
 int launch_wide_pack(const PackArgs& a, const float* mean_std, hipStream_t s);
 // Kernel-family dispatch (dispatch.cpp): the one place that says which minibatch kernel runs.
 // The shape class is fixed per handle (numbered as dppo_fused_plan reports it); within the tuned
 // class the kernel also depends on whether the caller wants the fused Adam tail.  capi.cpp
-// launches minibatch and evaluation kernels only through these.
+// launches minibatch, evaluation and actor kernels only through these.
 enum ShapeClass : int32_t { kShapeNone = 0, kShapeTuned = 1, kShapeWide = 2 };
 enum class MbKernel { None, Split /*mbwave.hip*/, Team /*mbstep.hip*/, Wide /*mbwide.hip*/ };
 bool tuned_shape(const MlpShape& sh);  // hidden 64, D <= 32, A <= 16
@@ -338,6 +342,10 @@ int launch_fused_eval(const MlpShape& sh, const ParamOffsets& po, const float* p
                       const float* obs, const void* actions, const float* next_obs, float* logp,
                       float* values, float* next_values, int64_t n, hipStream_t s,
                       EvalReuse* reuse = nullptr);
+// the rollout's action sampler of the shape's class: mlp.hip's act_kernel or wide_act_kernel
+int launch_fused_act(const MlpShape& sh, const ParamOffsets& po, const float* params,
+                     const float* obs, void* actions, int64_t n, uint64_t seed, uint64_t counter,
+                     hipStream_t s, float* heads = nullptr, const ActSquash* squash = nullptr);
 
 // One optimiser step as the host describes it: capi.cpp builds both structs, the launchers unpack
 // them into the kernels' parameter lists (FusedAdam included).

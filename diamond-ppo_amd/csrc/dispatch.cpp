@@ -1,8 +1,9 @@
 // Which fused kernel family runs for a shape: the tuned class (hidden 64, D <= 32) has the
 // sample-split kernel (mbwave.hip) where that kernel's own predicate admits the shape and the
 // two-team kernel (mbstep.hip) otherwise -- more actions, the fused Adam tail, DPPO_MB_LEGACY=1 --
-// with mlp.hip's evaluation; the wide class (hidden 128, or hidden 64 with 32 < D <= 128) has
-// mbwide.hip for both.  Host code only; the kernel files know nothing of each other.
+// with mlp.hip's evaluation and actor; the wide class (hidden 128, or hidden 64 with
+// 32 < D <= 128) has mbwide.hip for all three.  Host code only; the kernel files know nothing of
+// each other.
 #include "common.h"
 
 namespace dppo {
@@ -48,6 +49,14 @@ int launch_fused_eval(const MlpShape& sh, const ParamOffsets& po, const float* p
     return launch_eval(sh, po, params, obs, actions, next_obs, logp, values, next_values, n, s,
                        reuse);
   return launch_wide_eval(sh, po, params, obs, actions, next_obs, logp, values, next_values, n, s);
+}
+
+int launch_fused_act(const MlpShape& sh, const ParamOffsets& po, const float* params,
+                     const float* obs, void* actions, int64_t n, uint64_t seed, uint64_t counter,
+                     hipStream_t s, float* heads, const ActSquash* squash) {
+  if (tuned_shape(sh))
+    return launch_act(sh, po, params, obs, actions, n, seed, counter, s, heads, squash);
+  return launch_wide_act(sh, po, params, obs, actions, n, seed, counter, s, heads, squash);
 }
 
 }  // namespace dppo

@@ -1,5 +1,5 @@
-// Wide kernel family: the fused PPO minibatch step and the old-policy evaluation of the default
-// actor-critic MLP at hidden 128 (1 <= D <= 128) and at hidden 64 with 33 <= D <= 128, where the
+// Wide kernel family: the fused PPO minibatch step, the old-policy evaluation and the rollout's
+// action sampling of the default actor-critic MLP at hidden 128 (1 <= D <= 128) and at hidden 64 with 33 <= D <= 128, where the
 // tuned kernels (mbwave.hip / mbstep.hip / mlp.hip: hidden 64, D <= 32) do not apply.
 //
 // Reference: loss and backward of one minibatch, diamond/ppo.py:261-283 (continuous:
@@ -27,6 +27,7 @@
 // Every sum has a fixed order (MFMA accumulation over tiles in tile order, xor butterflies, fixed
 // LDS reductions); there are no floating-point atomics: two launches on the same inputs give the
 // same bits.
+#include "actdraw.h"
 #include "common.h"
 
 namespace dppo {
@@ -220,8 +221,9 @@ __device__ __forceinline__ void stage_heads(const WArgs& a, float* lds, bool con
   }
 }
 
-// hidden layers of one tile, X0 -> H1 -> H2 -> (HA), HC; ends behind a barrier
-template <int H>
+// hidden layers of one tile, X0 -> H1 -> H2 -> (HA), HC; ends behind a barrier.  CRITIC false (the
+// rollout sampler): HC is not computed
+template <int H, bool CRITIC = true>
 __device__ __forceinline__ void forward_tile(const WArgs& a, float* lds, int q, int lane,
                                              bool actor) {
   constexpr int SH = H + 4;
@@ -243,7 +245,7 @@ __device__ __forceinline__ void forward_tile(const WArgs& a, float* lds, int q, 
     fwd_mm<true>(P + a.po.Wa, H, H, H, lds + a.L.H2, SH, q, lane, acc);
     act_store<H>(acc, P + a.po.ba, lds + a.L.HA, q, lane);
   }
-  {
+  if (CRITIC) {
     f32x4 acc[2] = {};
     fwd_mm<true>(P + a.po.Wc, H, H, H, lds + a.L.H2, SH, q, lane, acc);
     act_store<H>(acc, P + a.po.bc, lds + a.L.HC, q, lane);
@@ -251,17 +253,12 @@ __device__ __forceinline__ void forward_tile(const WArgs& a, float* lds, int q, 
   __syncthreads();
 }
 
-// Heads of one sample on its H/8 lanes (8 hidden features each): out[16] (logits or Gaussian
-// mean; entries >= A are bo's zero padding) and the value, identical in every lane of the sample.
+// Actor head of one sample on its H/8 lanes (8 hidden features each): out[16] (logits or Gaussian
+// mean; entries >= A are bo's zero padding), identical in every lane of the sample.
 template <int H>
-__device__ __forceinline__ void heads_fwd(const WArgs& a, const float* lds, const float (&ha)[8],
-                                          const float (&hc)[8], int k0, bool actor,
-                                          float (&out)[16], float& v) {
+__device__ __forceinline__ void heads_actor(const WArgs& a, const float* lds, const float (&ha)[8],
+                                            int k0, bool actor, float (&out)[16]) {
   constexpr int LPS = H / 8;
-  float pv = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) pv += hc[j] * lds[a.L.WV + k0 + j];
-  v = sample_sum<LPS>(pv) + a.params[a.po.bv];
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     out[c] = 0.0f;
@@ -273,6 +270,19 @@ __device__ __forceinline__ void heads_fwd(const WArgs& a, const float* lds, cons
       out[c] = sample_sum<LPS>(p) + lds[a.L.BO + c];
     }
   }
+}
+
+// Both heads of one sample: the value (identical in every lane of the sample), then heads_actor
+template <int H>
+__device__ __forceinline__ void heads_fwd(const WArgs& a, const float* lds, const float (&ha)[8],
+                                          const float (&hc)[8], int k0, bool actor,
+                                          float (&out)[16], float& v) {
+  constexpr int LPS = H / 8;
+  float pv = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pv += hc[j] * lds[a.L.WV + k0 + j];
+  v = sample_sum<LPS>(pv) + a.params[a.po.bv];
+  heads_actor<H>(a, lds, ha, k0, actor, out);
 }
 
 // log-probability and entropy of one sample; discrete: p[], lp[] of the softmax; continuous:
@@ -596,6 +606,66 @@ __global__ __launch_bounds__(H * 4, 1) void wide_eval_kernel(WArgs a) {
   }
 }
 
+// Action sampling for the rollout (get_actions, ppo.py:73-82 / continuous_ppo.py:83-93) at wide
+// shapes: the actor half of wide_eval_kernel (X0 -> H1 -> H2 -> HA -> heads; no critic layer, no
+// value), then the draw of actdraw.h on lane li == 0 of each valid sample -- the stream of
+// mlp.hip's act_kernel.  Optional outputs: heads [n][A], actions (int32 [n] or float [n][A]) and,
+// with them, the squashed environment actions.
+struct WActArgs {
+  WArgs w;
+  float* heads;
+  void* actions;
+  float* env_act;
+  int squash;  // 1: tanh(u), 2: sq_lo + (tanh(u) + 1) * sq_half
+  float sq_lo[16], sq_half[16];
+  uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
+  int A;
+};
+
+template <int H, bool CONT>
+__global__ __launch_bounds__(H * 4, 1) void wide_act_kernel(WActArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int SH = H + 4;
+  constexpr int LPS = H / 8;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int hs = tid / LPS, li = tid % LPS, k0 = 8 * li;
+  const WArgs& w = a.w;
+  const WLds& L = w.L;
+  stage_heads<H>(w, lds, CONT);
+  const int64_t ntiles = (w.n + S - 1) / S;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t i = tile * S + hs;
+    const bool valid = i < w.n;
+    {
+      const float* src = w.obs + (valid ? i : 0) * w.D;
+      for (int k = li; k < w.D16; k += LPS)
+        lds[L.X0 + hs * L.SX + k] = (valid && k < w.D) ? src[k] : 0.0f;
+    }
+    __syncthreads();
+    forward_tile<H, false>(w, lds, q, lane, true);
+    float ha[8];
+    *(f32x4*)&ha[0] = *(const f32x4*)(lds + L.HA + hs * SH + k0);
+    *(f32x4*)&ha[4] = *(const f32x4*)(lds + L.HA + hs * SH + k0 + 4);
+    float out[16];
+    heads_actor<H>(w, lds, ha, k0, true, out);
+    if (valid && li == 0) {
+      if (a.heads) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+          if (c < a.A) a.heads[i * a.A + c] = out[c];
+      }
+      if (a.actions) {
+        if (CONT) {
+          draw_gaussian<16>(a, out, lds + L.LS, i, (float*)a.actions + i * a.A);
+        } else {
+          ((int32_t*)a.actions)[i] = draw_categorical<16>(a, out, i);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // Sample records for the wide minibatch gather, in pack_kernel's layout (gae.hip): one thread per
 // 16-B piece of a record; the advantage statistics come finalised in mean_std.
 struct WPackArgs {
@@ -667,6 +737,10 @@ void raise_wide_lds() {
     raise_dyn_lds((const void*)wide_eval_kernel<64, true>);
     raise_dyn_lds((const void*)wide_eval_kernel<128, false>);
     raise_dyn_lds((const void*)wide_eval_kernel<128, true>);
+    raise_dyn_lds((const void*)wide_act_kernel<64, false>);
+    raise_dyn_lds((const void*)wide_act_kernel<64, true>);
+    raise_dyn_lds((const void*)wide_act_kernel<128, false>);
+    raise_dyn_lds((const void*)wide_act_kernel<128, true>);
     return true;
   }();
   (void)attr;
@@ -759,6 +833,54 @@ int launch_wide_eval(const MlpShape& sh, const ParamOffsets& po, const float* pa
     }
     DPPO_LAUNCH_CHECK();
   }
+  return DPPO_OK;
+}
+
+int launch_wide_act(const MlpShape& sh, const ParamOffsets& po, const float* params,
+                    const float* obs, void* actions, int64_t n, uint64_t seed, uint64_t counter,
+                    hipStream_t s, float* heads, const ActSquash* squash) {
+  if (!wide_shape(sh)) {
+    set_error("wide actor kernel: unsupported shape");
+    return DPPO_EUNSUPPORTED;
+  }
+  if (n <= 0) return DPPO_OK;
+  WActArgs k{};
+  if (squash && squash->env_actions) {
+    if (!sh.continuous || sh.A > 16) {
+      set_error("tanh squash needs a continuous action space of at most 16 dims");
+      return DPPO_EINVAL;
+    }
+    k.env_act = squash->env_actions;
+    k.squash = squash->low && squash->high ? 2 : 1;
+    for (int j = 0; j < sh.A && k.squash == 2; ++j) {
+      k.sq_lo[j] = squash->low[j];
+      k.sq_half[j] = 0.5f * (squash->high[j] - squash->low[j]);
+    }
+  }
+  k.w = base_args(sh, po, params);
+  k.w.obs = obs;
+  k.w.n = n;
+  k.heads = heads;
+  k.actions = actions;
+  k.seed_lo = (uint32_t)seed;
+  k.seed_hi = (uint32_t)(seed >> 32);
+  k.ctr_lo = (uint32_t)counter;
+  k.ctr_hi = (uint32_t)(counter >> 32);
+  k.A = sh.A;
+  raise_wide_lds();
+  const bool c = sh.continuous != 0;
+  const int64_t ntiles = (n + S - 1) / S;
+  const int cus = cus_of(sh);
+  const dim3 grid((unsigned)(ntiles < cus ? ntiles : cus)), block((unsigned)(sh.H * 4));
+  const size_t lds = (size_t)k.w.L.total * sizeof(float);
+  if (sh.H == 128) {
+    if (c) DPPO_LAUNCH((wide_act_kernel<128, true>), grid, block, lds, s, k);
+    else DPPO_LAUNCH((wide_act_kernel<128, false>), grid, block, lds, s, k);
+  } else {
+    if (c) DPPO_LAUNCH((wide_act_kernel<64, true>), grid, block, lds, s, k);
+    else DPPO_LAUNCH((wide_act_kernel<64, false>), grid, block, lds, s, k);
+  }
+  DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }
 

@@ -20,8 +20,8 @@
 // walks 32-sample tiles; the layers are evaluated in an order that keeps at most two activation
 // blocks live (h1 -> h2 -> critic -> value -> actor -> heads), under the 128-VGPR budget of four
 // waves per SIMD.
+#include "actdraw.h"
 #include "common.h"
-#include "philox.h"
 
 namespace dppo {
 namespace {
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(kThreads, 4) void eval_kernel(KArgs a) {
 // actor forward, then Categorical(logits).sample() or Normal(mean, exp(log_std)).sample() on the
 // lane that holds the sample.  Randomness: Philox4x32-10 keyed by `seed`, counter (sample index,
 // call counter) -- a deterministic stream of its own (the reference draws from torch's generator:
-// same distribution, not the same draws).  The generator itself lives in philox.h.
+// same distribution, not the same draws).  The generator lives in philox.h, the draw in actdraw.h.
 struct ActArgs {
   LdsLayout L;
   ParamOffsets po;
@@ -592,67 +592,11 @@ __global__ __launch_bounds__(kThreads, 4) void act_kernel(ActArgs a) {
         if (k < a.A) a.heads[i * a.A + k] = out[k];
     }
     if (!a.actions) continue;
+    // the draw itself: actdraw.h (shared with mbwide.hip's wide_act_kernel)
     if (CONT) {
-      // Normal(mean, exp(log_std)).sample(): Box-Muller pairs from Philox (4 uniforms per call)
-      float* act = (float*)a.actions + i * a.A;
-#pragma unroll
-      for (int k0 = 0; k0 < AMAX; k0 += 4) {
-        if (k0 < a.A) {
-          uint32_t c[4] = {(uint32_t)i, (uint32_t)((uint64_t)i >> 32) ^ (uint32_t)(k0 << 24),
-                           a.ctr_lo, a.ctr_hi};
-          philox4x32(c, a.seed_lo, a.seed_hi);
-#pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            const float r = sqrtf(-2.0f * __logf(u01(c[2 * p])));
-            float sn, cs;
-            __sincosf(6.28318530717958647692f * u01(c[2 * p + 1]), &sn, &cs);
-            const int k = k0 + 2 * p;
-            const float u0 = k < AMAX ? out[k] + __expf(lds[L.ls + k]) * (r * cs) : 0.f;
-            const float u1 = k + 1 < AMAX ? out[k + 1] + __expf(lds[L.ls + k + 1]) * (r * sn) : 0.f;
-            if (k < a.A) act[k] = u0;
-            if (k + 1 < a.A) act[k + 1] = u1;
-            if (a.env_act) {
-              // the squashed env action (SURVEY 8 f2 extension; the reference samples the raw
-              // Gaussian, continuous_ppo.py:83-93): accurate tanhf, not the MLP's fast form
-              float* env = a.env_act + i * a.A;
-              if (k < a.A) {
-                const float t0 = tanhf(u0);
-                env[k] = a.squash == 2 ? a.sq_lo[k] + (t0 + 1.0f) * a.sq_half[k] : t0;
-              }
-              if (k + 1 < a.A) {
-                const float t1 = tanhf(u1);
-                env[k + 1] = a.squash == 2 ? a.sq_lo[k + 1] + (t1 + 1.0f) * a.sq_half[k + 1] : t1;
-              }
-            }
-          }
-        }
-      }
+      draw_gaussian<AMAX>(a, out, lds + L.ls, i, (float*)a.actions + i * a.A);
     } else {
-      // Categorical(logits).sample() by inverse CDF on one uniform
-      uint32_t c[4] = {(uint32_t)i, (uint32_t)((uint64_t)i >> 32), a.ctr_lo, a.ctr_hi};
-      philox4x32(c, a.seed_lo, a.seed_hi);
-      float mx = out[0];
-#pragma unroll
-      for (int k = 1; k < AMAX; ++k)
-        if (k < a.A) mx = fmaxf(mx, out[k]);
-      float e[AMAX], se = 0.0f;
-#pragma unroll
-      for (int k = 0; k < AMAX; ++k) {
-        e[k] = k < a.A ? __expf(out[k] - mx) : 0.0f;
-        se += e[k];
-      }
-      // the first k whose cumulative mass exceeds u * sum (the last action takes the remainder)
-      const float target = u01(c[0]) * se;
-      int pick = a.A - 1;
-      float cum = 0.0f;
-#pragma unroll
-      for (int k = 0; k < AMAX; ++k) {
-        if (k < a.A - 1) {
-          cum += e[k];
-          if (pick == a.A - 1 && target < cum) pick = k;
-        }
-      }
-      ((int32_t*)a.actions)[i] = pick;
+      ((int32_t*)a.actions)[i] = draw_categorical<AMAX>(a, out, i);
     }
   }
 }

@@ -10,7 +10,8 @@ anywhere in the reference: continuous_ppo.py:83-111,276-277).
 f2) makes ``rollout()`` send ``a = tanh(u)`` -- rescaled to the action space's bounds when they
 are finite -- to the environment while the experience keeps the Gaussian sample ``u``.  With the
 default network the squash is computed on the device by the same act-kernel launch that draws
-``u`` (``dppo_act_squash_f32``); a custom ``network_cls`` squashes on the host.  The
+``u`` (``dppo_act_squash_f32``: the tuned shape class, and the wide one once
+``fused_actions_wide`` is set); otherwise, and with a custom ``network_cls``, the host squashes.  The
 squashed policy's log-density is ``log N(u) - sum log(1 - tanh(u)^2)`` (:func:`squashed_log_prob`);
 the correction does not depend on the parameters, so it cancels in the PPO ratio and the update
 is exactly the unsquashed Gaussian update on ``u`` -- the same fused kernels, no second path.  The

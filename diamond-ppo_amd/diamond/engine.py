@@ -24,7 +24,9 @@ Two paths, chosen once per agent:
   rollout's actions in HIP too;
   **wide** -- hidden 128 with obs_dim <= 128, or hidden 64 with 32 < obs_dim <= 128, one rank
   (``csrc/mbwide.hip``): the same learn, while rollouts sample with ``network.get_actions`` as
-  the reference does.  ``DPPO_WIDE=0`` sends wide shapes down the generic path (A/B runs).
+  the reference does unless the agent opts in (``fused_actions_wide`` -> ``wide_act``): then
+  ``act()`` runs ``wide_act_kernel`` and draws the tuned class's Philox stream.
+  ``DPPO_WIDE=0`` sends wide shapes down the generic path (A/B runs).
 * **generic** -- any other ``network_cls`` (reference readme.md:89-111): the network's own
   methods run forward/backward under torch autograd on the GPU; GAE, advantage statistics and
   normalisation, and clip + Adam run in the HIP kernels (SURVEY.md §7.2 hard part 7).
@@ -348,7 +350,9 @@ def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1):
     """Which fused kernel family serves the default network at this shape: ``"tuned"`` (hidden 64,
     obs_dim <= 32), ``"wide"`` (hidden 128 with obs_dim <= 128, or hidden 64 with
     32 < obs_dim <= 128; one rank only) or ``None`` (the generic path).  The same predicate as
-    ``dppo_create`` (csrc/capi.cpp).  ``DPPO_WIDE=0`` turns the wide class off."""
+    ``dppo_create`` (csrc/capi.cpp).  ``DPPO_WIDE=0`` turns the wide class off.  Both classes have
+    a fused learn and fused actor kernels; ``NativeLearner.act()`` uses the wide class's only when
+    ``wide_act`` is set (its draws differ from ``network.get_actions``' torch stream)."""
     if not (1 <= act_dim <= 16 and obs_dim >= 1):
         return None
     if hidden == 64 and obs_dim <= 32:
@@ -392,9 +396,11 @@ class NativeLearner:
         self.shape_class = (fused_shape_class(int(cfg.network_hidden_dim), obs_dim, act_dim,
                                               self.world) if shapes_ok else None)
         self.fused = self.shape_class is not None
-        # the fused actor kernels (act()) exist for the tuned class only: wide shapes sample
-        # their rollouts with network.get_actions, as the reference does
+        # act() serves the tuned class; the wide class only once wide_act is set (rollout() sets
+        # it from the agent's fused_actions_wide): by default wide shapes sample their rollouts
+        # with network.get_actions, as the reference does
         self.fused_act = self.shape_class == "tuned"
+        self.wide_act = False
         if self.fused:
             self.flat = FlatParams(network, device, [L.offset[i] for i in range(L.count)], L.total)
         else:
@@ -540,15 +546,15 @@ class NativeLearner:
     # -----------------------------------------------------------------------------------------
     def act(self, observations: np.ndarray, seed: int, squash=None):
         """Sample actions for a batch of observations with the fused actor kernel
-        (``dppo_act_f32``; default network only): pinned upload, one launch, pinned download.
+        (``dppo_act_f32``; default network only -- the tuned class, or the wide class with
+        ``wide_act`` set): pinned upload, one launch, pinned download.
         Discrete actions come back int64 like the reference's ``Categorical.sample().numpy()``;
         continuous ones float32 ``[n, A]``.
 
         ``squash`` (continuous only, the tanh-squash extension): ``True`` for tanh(u), or a
         ``(low, high)`` pair of A-float bounds; then the same kernel launch also emits the
         environment's actions (``dppo_act_squash_f32``) and ``(u, env_actions)`` is returned."""
-        if not self.fused_act:
-            raise RuntimeError("act() needs the default network (fused path)")
+        self._require_act()
         if squash is not None and squash is not False:
             return self._act_squash(observations, seed, squash)
         obs = np.asarray(observations, dtype=np.float32).reshape(-1, self.D)
@@ -574,6 +580,10 @@ class NativeLearner:
         out = b["act_h"].numpy()
         return out.copy() if self.continuous else out.astype(np.int64)
 
+    def _require_act(self) -> None:
+        if not (self.fused_act or (self.shape_class == "wide" and self.wide_act)):
+            raise RuntimeError("act() needs the default network (fused path)")
+
     def _next_act_counter(self) -> int:
         """The Philox call counter of the action samplers: ONE sequence shared by act() and the
         squashing sampler, so no two calls with the same seed reuse a noise draw."""
@@ -582,6 +592,7 @@ class NativeLearner:
         return c
 
     def _act_squash(self, observations, seed, squash):
+        self._require_act()
         if not self.continuous:
             raise ValueError("tanh squash needs a continuous action space")
         obs = np.asarray(observations, dtype=np.float32).reshape(-1, self.D)

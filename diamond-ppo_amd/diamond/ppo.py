@@ -121,6 +121,13 @@ class _AgentBase:
     # (dppo_act_f32: same distribution as get_actions, Philox draws instead of torch's); False, or
     # any other network_cls, calls network.get_actions as the reference does
     fused_actions = True
+    # the same for the wide shape class (hidden 128, or hidden 64 with 32 < obs_dim <= 128), off
+    # by default because it replaces torch's action stream with the Philox one; set on the class
+    # or on an instance before rollout().  Measured on the stub env (profiles/wide_rollout.json,
+    # T = 32, N = 32 / 1024 / 8192): a rollout is 5.5x / 3.0x / 1.48x faster at LunarLander-128
+    # and 3.7x / 1.30x / 1.05x at Ant-64; the fused path lost at no measured shape or size, the
+    # last ratio is inside the run's spread
+    fused_actions_wide = False
 
     def _setup(self, env_fn, cfg, network_cls, envs=None):
         self.device = require_gpu(getattr(cfg, "device_index", 0))
@@ -183,8 +190,12 @@ class _AgentBase:
         if stager is not None:
             stager.begin()
         squash = self._squash_spec()
+        L = self._learner
+        L.wide_act = bool(self.fused_actions_wide)
+        fused_sampler = self.fused_actions and (
+            L.fused_act or (L.wide_act and L.shape_class == "wide"))
         for t in range(self.cfg.rollout_steps):
-            if self.fused_actions and self._learner.fused_act:
+            if fused_sampler:
                 if squash is None:
                     actions = self._learner.act(observations, self._act_seed)
                     env_actions = actions

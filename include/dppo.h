@@ -36,8 +36,7 @@ extern "C" {
 #define DPPO_EINVAL (-1)       /* invalid argument (Python: ValueError / AssertionError) */
 #define DPPO_EHIP (-2)         /* HIP runtime error (Python: RuntimeError) */
 #define DPPO_EUNSUPPORTED (-3) /* shape outside the fused kernels' support -- neither the tuned nor the wide
-                                  class of dims.hidden, or an actor call at a wide shape (Python:
-                                  NotImplementedError) */
+                                  class of dims.hidden (Python: NotImplementedError) */
 #define DPPO_ENOMEM (-4)       /* workspace allocation failed (Python: MemoryError) */
 #define DPPO_ECOMM (-5)        /* RCCL failure (Python: RuntimeError) */
 
@@ -60,8 +59,9 @@ typedef struct dppo_dims {
   int32_t act_dim;         /* discrete: action_space.n; continuous: prod(action_space.shape) */
   int32_t continuous;      /* 0 = PPO/Categorical, 1 = ContinuousPPO/JointNormal */
   int32_t hidden;          /* network_hidden_dim (ppo.py:32,51).  Fused kernels, act_dim <= 16: the tuned
-                              class at 64 with obs_dim <= 32; the wide class (world_size 1; no actor
-                              calls) at 128 with obs_dim <= 128 and at 64 with 32 < obs_dim <= 128 */
+                              class at 64 with obs_dim <= 32; the wide class (world_size 1) at 128
+                              with obs_dim <= 128 and at 64 with 32 < obs_dim <= 128.  Both serve the
+                              learn, evaluation and actor entry points */
   int32_t num_epochs;      /* ppo.py:25 */
   int32_t num_minibatches; /* ppo.py:26 */
   int32_t world_size;      /* ranks sharing the env axis (1 = single GPU) */
@@ -178,7 +178,9 @@ int dppo_old_policy_f32(dppo_handle* h, const float* params, const float* obs, c
  * obs [n][D] on the device; actions out int32 [n] or float32 [n][A].  Randomness: Philox4x32-10
  * keyed by `seed`, counter (sample index, `counter`) -- deterministic for a given
  * (seed, counter), the same distribution as the reference's torch draws but not the same draws;
- * advance `counter` once per call. */
+ * advance `counter` once per call.  Tuned and wide shapes (one stream definition for both, obs
+ * aligned to 4 bytes); DPPO_EUNSUPPORTED for a handle of neither class, which includes a wide
+ * shape with world_size > 1. */
 int dppo_act_f32(dppo_handle* h, const float* params, const float* obs, int64_t n, uint64_t seed,
                  uint64_t counter, void* actions, void* stream);
 
@@ -187,14 +189,14 @@ int dppo_act_f32(dppo_handle* h, const float* params, const float* obs, int64_t 
  * sample, continuous_ppo.py:83-93): actions [n][A] = the Gaussian samples u (the same draws as
  * dppo_act_f32 for this seed / counter; the experience keeps them), env_actions [n][A] =
  * low + (tanh(u) + 1) * (high - low) / 2 with low/high host arrays of A finite floats (high > low),
- * or tanh(u) when both are NULL. */
+ * or tanh(u) when both are NULL.  Shapes as dppo_act_f32. */
 int dppo_act_squash_f32(dppo_handle* h, const float* params, const float* obs, int64_t n,
                         uint64_t seed, uint64_t counter, const float* low, const float* high,
                         float* actions, float* env_actions, void* stream);
 
 /* The actor half of dppo_act_f32 without the draw: the logits (discrete, ppo.py:79) or Gaussian
  * means (continuous, continuous_ppo.py:88-90) of the default actor for obs [n][D], written to
- * heads [n][A] -- exactly the values dppo_act_f32 samples from. */
+ * heads [n][A] -- exactly the values dppo_act_f32 samples from.  Shapes as dppo_act_f32. */
 int dppo_actor_forward_f32(dppo_handle* h, const float* params, const float* obs, int64_t n,
                            float* heads, void* stream);
 
