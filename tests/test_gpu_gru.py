@@ -4,8 +4,10 @@ f4) against the float64 autograd restatement of the reference's intended semanti
 no golden trace exists).
 
 Tolerances: gradients max|diff| <= 2e-5 x max|g| per tensor group (fp32 sums over up to 1,024
-samples and 32 BPTT steps); loss sums rel 1e-5.  learn(): fused vs the torch-autograd path of the
-same agent -- parameters within 2e-5 after 2 x 2 Adam steps."""
+samples and 32 BPTT steps); loss sums rel 1e-5.  The edge cases (tests/gru_cases.py, at most 198
+samples and 9 steps) keep those tolerances.  learn(): fused vs the torch-autograd path of the
+same agent -- parameters within 2e-5 after 2 x 2 Adam steps; against the oracle's learn() in
+tests/test_gpu_gru_learn.py."""
 import ctypes
 
 import numpy as np
@@ -15,6 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import diamond
+import gru_cases
 from diamond import _native as N
 from oracle import gru_torch as GT
 
@@ -53,28 +56,44 @@ def test_gru_minibatch_gradient_matches_float64_oracle(T, Nn, D, A, frac):
     B = T * Nn
     m = max(1, int(B * frac))
     mb_idx = np.random.default_rng(7).permutation(B)[:m].astype(np.int32)
+    _check_against_oracle(agent, x, mb_idx, m, 0.15, 1.0, 0.01)
+
+
+def _kernel_grad(agent, x, mb_idx, m_total, clip, vf, ent):
+    """One dppo_gru_minibatch_grad_f32 launch on the agent's parameters: the flat gradient with
+    the three loss sums behind it, as a device tensor."""
     dev = agent.device
+    m = len(mb_idx)
     t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in x.items()}
     t["prev_dones"] = t["prev_dones"].to(torch.uint8)
     batch = N.GruBatch(*[t[k].data_ptr() for k in ("obs", "actions", "old_log_probs",
                                                       "advantages", "returns", "prev_dones",
                                                       "hx0")])
-    idx = torch.from_numpy(mb_idx).to(dev)
-    hp = N.HParams(gamma=0.99, gae_lambda=0.95, ppo_clip=0.15, value_loss_weight=1.0,
-                   entropy_beta=0.01, grad_norm_clip=0.5, adam_beta1=0.9, adam_beta2=0.999,
+    # never an empty tensor: the C ABI refuses a NULL idx also where m = 0
+    idx = torch.from_numpy(mb_idx if m else np.zeros(1, np.int32)).to(dev)
+    hp = N.HParams(gamma=0.99, gae_lambda=0.95, ppo_clip=clip, value_loss_weight=vf,
+                   entropy_beta=ent, grad_norm_clip=0.5, adam_beta1=0.9, adam_beta2=0.999,
                    adam_eps=1e-5, advantage_norm=1, lr=3e-4, adam_step=0)
-    L = agent.gru.layout
-    grad = torch.zeros(L.total + 8, device=dev)
+    grad = torch.zeros(agent.gru.layout.total + 8, device=dev)
     N.check(agent.gru.lib.dppo_gru_minibatch_grad_f32(
-        agent.gru.h, agent.flat.flat.data_ptr(), ctypes.byref(batch), idx.data_ptr(), m, m,
+        agent.gru.h, agent.flat.flat.data_ptr(), ctypes.byref(batch), idx.data_ptr(), m, m_total,
         ctypes.byref(hp), grad.data_ptr(), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
+    return grad
+
+
+def _check_against_oracle(agent, x, mb_idx, m_total, clip, vf, ent):
+    """The kernel and the float64 oracle on the same data, selection, divisor and loss
+    hyperparameters.  Returns the kernel's output (device tensor) and the oracle's gradients."""
+    m = len(mb_idx)
+    L = agent.gru.layout
+    grad = _kernel_grad(agent, x, mb_idx, m_total, clip, vf, ent)
     g = grad.cpu().numpy()
     params = {n: p.detach().cpu().numpy() for n, p in agent.network.named_parameters()}
     assert list(params) == GT.GRU_NAMES
     sums, ref = GT.minibatch_grads(params, x["obs"], x["actions"], x["old_log_probs"],
                                    x["advantages"], x["returns"], x["prev_dones"], x["hx0"],
-                                   mb_idx, m)
+                                   mb_idx, m_total, clip, vf, ent)
     scale = max(np.abs(r).max() for r in ref.values())
     for i, n in enumerate(GT.GRU_NAMES):
         got = g[L.offset[i]:L.offset[i] + L.numel[i]].reshape(ref[n].shape)
@@ -82,12 +101,70 @@ def test_gru_minibatch_gradient_matches_float64_oracle(T, Nn, D, A, frac):
         assert err <= 2e-5 * scale, (n, err, scale)
     np.testing.assert_allclose(g[L.total:L.total + 3], sums, rtol=1e-5, atol=1e-5 * m)
     # deterministic: the same call twice gives the same bits
-    g2 = torch.zeros_like(grad)
-    N.check(agent.gru.lib.dppo_gru_minibatch_grad_f32(
-        agent.gru.h, agent.flat.flat.data_ptr(), ctypes.byref(batch), idx.data_ptr(), m, m,
-        ctypes.byref(hp), g2.data_ptr(), torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
+    g2 = _kernel_grad(agent, x, mb_idx, m_total, clip, vf, ent)
     assert torch.equal(grad, g2)
+    return grad, ref
+
+
+_case_agents = {}
+
+
+def _case_agent(case, params):
+    """One agent per shape, shared by the cases (each loads its own weights; whatever an earlier
+    case left in the handle's scratch must not show)."""
+    if case.shape not in _case_agents:
+        _case_agents[case.shape] = _agent(*case.shape)
+    agent = _case_agents[case.shape]
+    assert agent.gru is not None
+    with torch.no_grad():
+        for n, p in agent.network.named_parameters():
+            p.copy_(torch.from_numpy(params[n]))
+    return agent
+
+
+@pytest.mark.parametrize("case", gru_cases.CASES, ids=str)
+def test_gru_minibatch_gradient_edge_cases(case):
+    """tests/gru_cases.py: sample counts per workgroup that are no multiple of the MFMA's k = 4
+    (tile_sum's masked last step), D and A just under and at the kernel's limits, a last workgroup
+    of one and two envs, loss hyperparameters and divisors other than the defaults, the structural
+    dones patterns, single-sample selections and an on-policy batch; each guarded away from the
+    surrogate's kink by conditions evaluated on the oracle alone."""
+    params, x, mb_idx, m_total = gru_cases.build(case)
+    gru_cases.guards(case, params, x, mb_idx)
+    agent = _case_agent(case, params)
+    grad, ref = _check_against_oracle(agent, x, mb_idx, m_total, case.clip, case.vf, case.ent)
+    T, Nn = case.shape[:2]
+    if case.dones == "first":
+        # every env starts the rollout reset: hx0 has no effect and gets no gradient
+        x2 = dict(x, hx0=np.random.default_rng(11).standard_normal(x["hx0"].shape)
+                  .astype(np.float32) * 2)
+        assert np.abs(x2["hx0"] - x["hx0"]).min() > 0
+        assert torch.equal(_kernel_grad(agent, x2, mb_idx, m_total, case.clip, case.vf, case.ent),
+                           grad)
+    if case.pick is not None:
+        # the recurrent weights see the sample through every earlier step, or through none: with
+        # no dones and t = T-1 the oracle's Whh gradient is dense; at t = 0 it is the one outer
+        # product with the initial hidden state
+        whh = ref["gru.weight_hh_l0"]
+        assert np.count_nonzero(whh) == whh.size
+        if case.pick[0] == 0:
+            assert np.linalg.matrix_rank(whh, tol=1e-12 * np.abs(whh).max()) == 1
+        else:
+            assert np.linalg.matrix_rank(whh, tol=1e-12 * np.abs(whh).max()) > 1
+
+
+def test_gru_minibatch_empty_selection_after_full_batch():
+    """m = 0 on a handle whose scratch holds a full-batch call: every gradient entry and the three
+    loss sums are exactly 0."""
+    case = next(c for c in gru_cases.CASES if c.name == "ktail-7x17x5x3-1.0")
+    params, x, mb_idx, m_total = gru_cases.build(case)
+    agent = _case_agent(case, params)
+    full = _kernel_grad(agent, x, mb_idx, m_total, case.clip, case.vf, case.ent)
+    total = agent.gru.layout.total
+    assert torch.count_nonzero(full[:total + 3]).item() > total // 2
+    for m_tot in (1, len(mb_idx)):
+        empty = _kernel_grad(agent, x, mb_idx[:0], m_tot, case.clip, case.vf, case.ent)
+        assert torch.count_nonzero(empty).item() == 0
 
 
 def test_recurrent_learn_fused_matches_torch_path():
