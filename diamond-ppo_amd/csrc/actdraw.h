@@ -10,7 +10,8 @@
 namespace dppo {
 
 // What the draw reads from the kernel's argument struct (ARGS): the Philox key and call counter
-// {seed_lo, seed_hi, ctr_lo, ctr_hi}, A, and for the Gaussian {env_act, squash, sq_lo[], sq_half[]}.
+// {seed_lo, seed_hi, ctr_lo, ctr_hi}, A, and for the Gaussian {env_act, squash, sq_lo[], sq_half[],
+// sq_hi[]}.
 
 // Categorical(logits).sample() by inverse CDF on one uniform
 template <int AMAX, class ARGS>
@@ -48,7 +49,8 @@ __device__ __forceinline__ int draw_categorical(const ARGS& a, const float (&out
 // draws u.  a.env_act (or null): the [n][A] environment actions, tanh(u) (squash 1) or
 // sq_lo + (tanh(u) + 1) * sq_half (squash 2) -- the squashed env action (SURVEY 8 f2 extension;
 // the reference samples the raw Gaussian, continuous_ppo.py:83-93): accurate tanhf, not the MLP's
-// fast form.
+// fast form.  Capped at sq_hi: where tanhf returns 1, low + 2 * ((high - low) / 2) can round one
+// ulp above high, outside the action space.
 template <int AMAX, class ARGS>
 __device__ __forceinline__ void draw_gaussian(const ARGS& a, const float (&out)[AMAX],
                                               const float* ls, int64_t i, float* act) {
@@ -73,11 +75,13 @@ __device__ __forceinline__ void draw_gaussian(const ARGS& a, const float (&out)[
           float* env = a.env_act + i * A;
           if (k < A) {
             const float t0 = tanhf(u0);
-            env[k] = a.squash == 2 ? a.sq_lo[k] + (t0 + 1.0f) * a.sq_half[k] : t0;
+            const float e0 = fminf(a.sq_lo[k] + (t0 + 1.0f) * a.sq_half[k], a.sq_hi[k]);
+            env[k] = a.squash == 2 ? e0 : t0;
           }
           if (k + 1 < A) {
             const float t1 = tanhf(u1);
-            env[k + 1] = a.squash == 2 ? a.sq_lo[k + 1] + (t1 + 1.0f) * a.sq_half[k + 1] : t1;
+            const float e1 = fminf(a.sq_lo[k + 1] + (t1 + 1.0f) * a.sq_half[k + 1], a.sq_hi[k + 1]);
+            env[k + 1] = a.squash == 2 ? e1 : t1;
           }
         }
       }

@@ -617,7 +617,7 @@ struct WActArgs {
   void* actions;
   float* env_act;
   int squash;  // 1: tanh(u), 2: sq_lo + (tanh(u) + 1) * sq_half
-  float sq_lo[16], sq_half[16];
+  float sq_lo[16], sq_half[16], sq_hi[16];
   uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
   int A;
 };
@@ -855,6 +855,7 @@ int launch_wide_act(const MlpShape& sh, const ParamOffsets& po, const float* par
     for (int j = 0; j < sh.A && k.squash == 2; ++j) {
       k.sq_lo[j] = squash->low[j];
       k.sq_half[j] = 0.5f * (squash->high[j] - squash->low[j]);
+      k.sq_hi[j] = squash->high[j];
     }
   }
   k.w = base_args(sh, po, params);

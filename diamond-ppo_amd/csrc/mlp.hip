@@ -532,7 +532,7 @@ struct ActArgs {
   // tanh(u) (squash 1) or low + (tanh(u) + 1) * (high - low) / 2 (squash 2)
   float* env_act;
   int squash;
-  float sq_lo[16], sq_half[16];
+  float sq_lo[16], sq_half[16], sq_hi[16];
   int64_t n;
   uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
   int D, D8, nq1, A;
@@ -710,6 +710,7 @@ int launch_act(const MlpShape& sh, const ParamOffsets& po, const float* params, 
     for (int j = 0; j < sh.A && k.squash == 2; ++j) {
       k.sq_lo[j] = squash->low[j];
       k.sq_half[j] = 0.5f * (squash->high[j] - squash->low[j]);
+      k.sq_hi[j] = squash->high[j];
     }
   }
   k.L = make_layout(sh);

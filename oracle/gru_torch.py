@@ -68,11 +68,13 @@ def log_probs(params, obs, actions, prev_dones, hx0):
 
 
 def minibatch_grads(params, obs, actions, old_log_probs, advantages, returns, prev_dones, hx0,
-                    mb_idx, m_total, clip=0.15, vf=1.0, ent=0.01):
+                    mb_idx, m_total, clip=0.15, vf=1.0, ent=0.01, dt=torch.float64):
     """(loss sums {policy, value, entropy}, grads dict) in float64 for the samples mb_idx (flat
-    t * N + n) of one rollout, divided by m_total (recurrent_ppo.py:337-358)."""
-    p = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in params.items()}
-    d = lambda x: torch.as_tensor(np.asarray(x), dtype=torch.float64)
+    t * N + n) of one rollout, divided by m_total (recurrent_ppo.py:337-358).  ``dt=torch.float32``
+    evaluates the same graph in float32: torch's own float32 error, the yardstick of a float32
+    kernel's distance from the float64 result."""
+    p = {k: torch.tensor(np.asarray(v), dtype=dt, requires_grad=True) for k, v in params.items()}
+    d = lambda x: torch.as_tensor(np.asarray(x), dtype=dt)
     logits, values = sequence(p, d(obs), torch.as_tensor(np.asarray(prev_dones, bool)), d(hx0))
     A = logits.shape[-1]
     lg = logits.reshape(-1, A)[mb_idx]

@@ -174,18 +174,31 @@ def new_policy_logp64(params, obs, act, cont):
     return P.categorical_logp_entropy(f["out"], act, np.float64)[0]
 
 
-def offpolicy_inputs(L, names, D, A, cont, T, Nn, m, hyper, s, seed):
+def flat32(L, names, params):
+    """The parameters in the library's flat float32 layout."""
+    flat = np.zeros(L.total, np.float32)
+    for i, n in enumerate(names):
+        flat[L.offset[i]:L.offset[i] + L.numel[i]] = params[n].ravel()
+    return flat
+
+
+def offpolicy_inputs(L, names, D, A, cont, T, Nn, m, hyper, s, seed, transform=None):
     """Old and new parameters, a rollout and a stratified minibatch index list for one off-policy
     gradient check.  Everything is the oracle's: old log-probs, values, GAE and (if
     hyper.advantage_norm) the normalised advantages in float32 as learn() computes them, the
     ratio exp(logp_new - logp_old) with the new log-prob in float64.  idx takes up to m / 5
-    samples of each regime, then fills at random, never from the excluded samples."""
+    samples of each regime, then fills at random, never from the excluded samples.
+    ``transform(params, obs, next_obs, actions, rewards)`` (tests/regime_cases.py) moves the old
+    parameters and the rollout into a numerical regime before the new parameters are drawn."""
     B = T * Nn
     rng = np.random.default_rng(1000 + seed)
     old, old_flat = random_params(L, names, D, A, cont, rng)
-    new, new_flat = perturbed_params(L, names, old, s, rng)
     host = synth_host(T, Nn, D, A, cont, 2000 + seed,
                       reward_mean=1.0 if hyper.advantage_norm else 0.0)
+    if transform is not None:
+        old, *data = transform(old, *host[:4])
+        old_flat, host = flat32(L, names, old), (*data, *host[4:])
+    new, new_flat = perturbed_params(L, names, old, s, rng)
     obs, nobs, act, rew, te, tr = host
     logp_old, v, nv, _ = P.old_policy(old, obs, act, nobs, cont)
     adv = P.gae(rew, te, tr, v, nv, hyper.gamma, hyper.gae_lambda)

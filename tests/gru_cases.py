@@ -31,6 +31,13 @@ class Case:
     m_total_mul: int = 1         # m_total = mul * m (the data-parallel union minibatch)
     dones: str = "random"        # random | none | first | env_always | last
     on_policy: bool = False
+    # numerical regimes (tests/regime_cases.py); the defaults leave a case as it was
+    obs_scale: float = 1.0       # on the observations
+    gru_scale: float = 1.0       # on gru.weight_ih_l0 and gru.weight_hh_l0 (gates, candidate)
+    actor_scale: float = 1.0     # on actor_head.2.weight (the logits)
+    ret_scale: float = 1.0       # on the returns
+    old_noise: float = 0.0       # > 0: old log-probs = the parameters' own + old_noise * N(0, 1)
+    seed_shift: int = 0          # added to the shape's seed (weights and data)
 
     def __str__(self):
         return self.name
@@ -78,14 +85,29 @@ def data(T, Nn, D, A, seed):
                 hx0=(rng.standard_normal((Nn, G)) * 0.5).astype(np.float32))
 
 
+def scaled_params(params, case):
+    """The parameters with the case's regime scales on the GRU and actor output weights."""
+    params = dict(params)
+    for n, k in (("gru.weight_ih_l0", case.gru_scale), ("gru.weight_hh_l0", case.gru_scale),
+                 ("actor_head.2.weight", case.actor_scale)):
+        if k != 1.0:
+            params[n] = params[n] * np.float32(k)
+    return params
+
+
 def build(case):
     """(params, data dict, mb_idx int32, m_total) of one case."""
     T, Nn, D, A = case.shape
-    seed = T * 100 + Nn
+    seed = T * 100 + Nn + case.seed_shift
     rng = np.random.default_rng(seed + 1)
     params = {n: (p + 0.3 * rng.standard_normal(p.shape)).astype(np.float32)
               for n, p in initial_params(D, A).items()}
     x = data(T, Nn, D, A, seed)
+    params = scaled_params(params, case)
+    if case.obs_scale != 1.0:
+        x["obs"] = x["obs"] * np.float32(case.obs_scale)
+    if case.ret_scale != 1.0:
+        x["returns"] = x["returns"] * np.float32(case.ret_scale)
     pd = x["prev_dones"]
     if case.dones == "none":
         pd[:] = False
@@ -101,6 +123,10 @@ def build(case):
     if case.on_policy:
         lp = GT.log_probs(params, x["obs"], x["actions"], pd, x["hx0"])
         x["old_log_probs"] = lp.astype(np.float32)
+    elif case.old_noise > 0.0:
+        lp = GT.log_probs(params, x["obs"], x["actions"], pd, x["hx0"])
+        noise = np.random.default_rng(seed + 2).standard_normal(lp.shape)
+        x["old_log_probs"] = (lp + case.old_noise * noise).astype(np.float32)
     B = T * Nn
     if case.pick is not None:
         mb_idx = np.array([case.pick[0] * Nn + case.pick[1]], np.int32)

@@ -70,7 +70,17 @@ CASES = {
     "flags": (MID, dict(num_epochs=2, num_minibatches=7), (3,), True, None),
     "two-learns-decay": (MID, dict(num_epochs=2, num_minibatches=1, decay_lr=True,
                                    total_steps=3 * MID[0] * MID[1]), (3, 4), False, 2e-5),
+    # numerical regimes (tests/regime_cases.py): REGIME below scales the observations / the
+    # actor's output layer of these two
+    "regime-obs100": (MID, dict(num_epochs=2, num_minibatches=7), (3,), False, None),
+    "regime-peaked20": (MID, dict(num_epochs=2, num_minibatches=7), (3,), False, None),
 }
+# case -> gru_cases.Case regime fields.  The initial actor output layer has gain 0.01 on heads of
+# norm about 1: the scale that brings the largest logit gap of the rollout to 66, peaked20's range
+# (>= 55), is 7000 (the oracle gives 18.9 at 2000); its old log-probs are the initial policy's
+# own.  The orthogonal base layer on 5 inputs needs observations x 100 to saturate 0.8 of its
+# units.  tests/test_regimes_cpu.py asserts both from the oracle.
+REGIME = {"regime-obs100": dict(obs_scale=100.0), "regime-peaked20": dict(actor_scale=7000.0)}
 TERM_ENV, TRUNC_ENV = 0, 1
 
 
@@ -92,7 +102,24 @@ def _experience(name, call, device):
             term[TERM_ENV] = True
             trunc[TRUNC_ENV] = t == T // 2
             row[3], row[4] = term, trunc
+    k = REGIME.get(name, {}).get("obs_scale", 1.0)
+    if k != 1.0:
+        for row in exp:
+            row[0] = row[0] * k
+    if "actor_scale" in REGIME.get(name, {}):
+        # on-policy old log-probs (the initial parameters' own): against synth_experience's
+        # -1 .. -0.3 every ratio of a sharp policy would be exp(-50) or e
+        x = GT.stack_experience(exp)
+        params = _initial_params(name, D, A, _config(name).seed)
+        lp = GT.log_probs(params, x["obs"], x["actions"], x["prev_dones"], x["hx0"])
+        for t, row in enumerate(exp):
+            row[6] = torch.as_tensor(lp[t], dtype=torch.float32, device=device)
     return exp
+
+
+def _initial_params(name, D, A, seed):
+    case = gru_cases.Case(name, CASES[name][0], **REGIME.get(name, {}))
+    return gru_cases.scaled_params(gru_cases.initial_params(D, A, seed), case)
 
 
 def _perms(name, call):
@@ -108,7 +135,7 @@ def _oracle(name):
     the LR after its scheduler step."""
     (T, Nn, D, A), _, seeds, _, _ = CASES[name]
     cfg = _config(name)
-    params = gru_cases.initial_params(D, A, cfg.seed)
+    params = _initial_params(name, D, A, cfg.seed)
     adam = ppo_np.new_adam_state(params, GT.GRU_NAMES)
     lr, calls = cfg.lr, []
     for call in range(len(seeds)):
@@ -140,6 +167,11 @@ def _run(name, fused):
     init = gru_cases.initial_params(D, A, agent.cfg.seed)
     for n, p in agent.network.named_parameters():
         assert np.array_equal(p.detach().cpu().numpy(), init[n]), n
+    if name in REGIME:
+        init = _initial_params(name, D, A, agent.cfg.seed)
+        with torch.no_grad():
+            for n, p in agent.network.named_parameters():
+                p.copy_(torch.from_numpy(init[n]))
     captured = []
     inner = agent._learn_fused
 

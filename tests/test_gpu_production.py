@@ -46,7 +46,7 @@ from diamond import _native as N
 from oracle import ppo_np as P
 
 from gpu_helpers import (H, SpecEnvs, dev, hparams, production_depth, random_params, stream,
-                         synth)
+                         synth, to_device)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -156,16 +156,28 @@ def test_full_size_old_policy_and_records_vs_oracle(name, T, Nn, D, A, cont):
 
 
 # ---------------------------------------------------------------------------------------------
-def learn_vs_oracle(T, Nn, D, A, cont, seed):
+def learn_vs_oracle(T, Nn, D, A, cont, seed, transform=None, hidden=None):
+    """One learn() of a fresh agent against the oracle's.  ``transform(params, obs, next_obs,
+    actions, rewards)`` (tests/regime_cases.py; default: identity) replaces the agent's initial
+    parameters and the synthetic rollout; ``hidden`` is the network's hidden width."""
     Cfg = diamond.ContinuousPPOConfig if cont else diamond.PPOConfig
     Agent = diamond.ContinuousPPO if cont else diamond.PPO
-    cfg = Cfg(rollout_steps=T, num_envs=Nn, verbose=False)
+    kw = {} if hidden is None else dict(network_hidden_dim=hidden)
+    cfg = Cfg(rollout_steps=T, num_envs=Nn, verbose=False, **kw)
     agent = Agent(None, cfg, envs=SpecEnvs(D, A, cont))
     assert agent._learner.fused
     mb = T * Nn // cfg.num_minibatches
     names = [n for n, _ in agent.network.named_parameters()]
     params = {n: p.detach().cpu().numpy().copy() for n, p in agent.network.named_parameters()}
     ro, host = synth(T, Nn, D, A, cont, seed)
+    if transform is not None:
+        params, *data = transform(params, *host[:4])
+        host = (*data, *host[4:])
+        ro = to_device(host)
+        with torch.no_grad():
+            for n, p in agent.network.named_parameters():
+                p.copy_(torch.from_numpy(params[n]))
+        params = {n: v.copy() for n, v in params.items()}
     np.random.seed(seed)
     st = np.random.get_state()
     agent.learn_device(ro)
