@@ -23,6 +23,10 @@
 //  F  weight gradients = sums over the workgroup's samples of outer products, on MFMA
 //     (v_mfma_f32_16x16x4_f32, k = sample) in a fixed order; bias sums on VALU; one slab per
 //     workgroup (optim.hip's slab reduction sums them in a fixed order: bit-reproducible).
+//
+// gru_grad_kernel is the G = 16 kernel.  G = 32 and 64 run gruwide.hip's kernel (same phases and
+// scratch contract, another mapping) and gruactwide.hip's rollout steps; the host code below
+// (validation, layout, workspace, C ABI) serves all three widths and dispatches on G.
 #include <cstring>
 #include <vector>
 
@@ -535,9 +539,11 @@ __global__ void mask_kernel(const int32_t* __restrict__ idx, int m, float* __res
 
 }  // namespace
 
-size_t gru_lds_bytes(int D) { return (size_t)gru_lds(D).total * sizeof(float); }
+size_t gru_lds_bytes(int D, int G) {
+  return G == kG ? (size_t)gru_lds(D).total * sizeof(float) : gruw_lds_bytes(D, G);
+}
 
-int launch_gru_grad(const GruOffsets& po, const float* params, const dppo_gru_batch& b,
+int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
                     const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
                     int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
                     float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s) {
@@ -548,6 +554,9 @@ int launch_gru_grad(const GruOffsets& po, const float* params, const dppo_gru_ba
     DPPO_LAUNCH(mask_kernel, dim3(g), dim3(256), 0, s, idx, m, wmask);
     DPPO_LAUNCH_CHECK();
   }
+  if (G != kG)
+    return launch_gruw_grad(G, po, params, b, wmask, T, N, D, A, inv_m, clip_eps, vf, ent, sc,
+                            slabs, slab_stride, p_total, s);
   GruArgs a{};
   a.po = po;
   a.params = params;
@@ -566,14 +575,16 @@ int launch_gru_grad(const GruOffsets& po, const float* params, const dppo_gru_ba
   a.slabs = slabs;
   a.slab_stride = slab_stride;
   a.p_total = p_total;
-  const size_t lds = gru_lds_bytes(D);
-  const int grid = (N + kEnvs - 1) / kEnvs;
+  const size_t lds = gru_lds_bytes(D, kG);
+  const int grid = gru_grid(N, kG);
   DPPO_LAUNCH(gru_grad_kernel, dim3(grid), dim3(kThr), lds, s, a);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }
 
-int gru_grid(int N) { return (N + kEnvs - 1) / kEnvs; }
+int gru_envs(int G) { return G == kG ? kEnvs : gruw_envs(G); }
+
+int gru_grid(int N, int G) { return (N + gru_envs(G) - 1) / gru_envs(G); }
 
 }  // namespace dppo
 
@@ -608,16 +619,19 @@ struct dppo_gru_handle {
 namespace {
 
 int gru_validate(const dppo_gru_dims* d) {
-  if (!d || d->rollout_steps < 1 || d->num_envs < 1 || d->obs_dim < 1 || d->act_dim < 1) {
+  if (!d || d->rollout_steps < 1 || d->num_envs < 1 || d->obs_dim < 1 || d->act_dim < 1 ||
+      d->gru_hidden < 1) {
     set_error("invalid dppo_gru_dims");
     return DPPO_EINVAL;
   }
-  if (d->hidden != kH || d->gru_hidden != kG || d->obs_dim > 32 || d->act_dim > kAPad) {
-    set_error("fused GRU kernels support hidden=64, gru_hidden=16, obs_dim<=32, act_dim<=16 "
+  if (d->hidden != kH || !(d->gru_hidden == kG || gruw_width(d->gru_hidden)) || d->obs_dim > 32 ||
+      d->act_dim > kAPad) {
+    set_error("fused GRU kernels support hidden=64, gru_hidden in {16, 32, 64}, obs_dim<=32, "
+              "act_dim<=16 "
               "(got H=%d G=%d D=%d A=%d)", d->hidden, d->gru_hidden, d->obs_dim, d->act_dim);
     return DPPO_EUNSUPPORTED;
   }
-  if ((int64_t)d->rollout_steps * d->num_envs > 0x7FFFFFFF / 64) {
+  if ((int64_t)d->rollout_steps * d->num_envs > 0x7FFFFFFF / (4 * d->gru_hidden)) {
     set_error("T*N too large for the GRU workspace");
     return DPPO_EINVAL;
   }
@@ -626,10 +640,10 @@ int gru_validate(const dppo_gru_dims* d) {
 
 void gru_layout(const dppo_gru_dims* d, dppo_layout* L) {
   std::memset(L, 0, sizeof(*L));
-  const int D = d->obs_dim, A = d->act_dim;
+  const int D = d->obs_dim, A = d->act_dim, G = d->gru_hidden;
   // RecurrentActorCriticNetwork.named_parameters() order (diamond/recurrent_ppo.py)
-  const int rc[14][2] = {{kH, D}, {kH, 1}, {3 * kG, kH}, {3 * kG, kG}, {3 * kG, 1}, {3 * kG, 1},
-                         {kH, kG}, {kH, 1}, {A, kH}, {A, 1}, {kH, kG}, {kH, 1}, {1, kH}, {1, 1}};
+  const int rc[14][2] = {{kH, D}, {kH, 1}, {3 * G, kH}, {3 * G, G}, {3 * G, 1}, {3 * G, 1},
+                         {kH, G}, {kH, 1}, {A, kH}, {A, 1}, {kH, G}, {kH, 1}, {1, kH}, {1, 1}};
   int64_t off = 0, real = 0;
   for (int i = 0; i < 14; ++i) {
     const int64_t ne = (int64_t)rc[i][0] * rc[i][1];
@@ -713,12 +727,13 @@ int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out
   h->po = GruOffsets{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11],
                      o[12], o[13]};
   h->B = (int64_t)dims->rollout_steps * dims->num_envs;
-  h->G = gru_grid(dims->num_envs);
+  const int G = dims->gru_hidden;
+  h->G = gru_grid(dims->num_envs, G);
   h->slab_stride = (h->layout.total + 8 + 63) / 64 * 64;
   const int D16 = (dims->obs_dim + 15) / 16 * 16;
-  // per-sample rows: obs D16 | x1 64 | gi 48 | hi ho r z n ghn 6x16 | ya yc 2x64 | dl dv 2x16 |
-  // dya dyc 2x64 | dho 16 | dgi dgh 2x48 | dx1 64
-  const int64_t row = D16 + kH + 3 * kG + 6 * kG + 2 * kH + 2 * kAPad + 2 * kH + kG + 6 * kG + kH;
+  // per-sample rows: obs D16 | x1 64 | gi 3G | hi ho r z n ghn 6xG | ya yc 2x64 | dl dv 2x16 |
+  // dya dyc 2x64 | dho G | dgi dgh 2x3G | dx1 64
+  const int64_t row = D16 + kH + 3 * G + 6 * G + 2 * kH + 2 * kAPad + 2 * kH + G + 6 * G + kH;
   hipError_t e = hipMalloc((void**)&h->scratch, (size_t)(h->B * row) * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&h->wmask, (size_t)h->B * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&h->slabs, (size_t)(h->G * h->slab_stride) * sizeof(float));
@@ -740,22 +755,22 @@ int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out
   GruScratch& sc = h->sc;
   sc.obs = take(D16);
   sc.x1 = take(kH);
-  sc.gi = take(3 * kG);
-  sc.hi = take(kG);
-  sc.ho = take(kG);
-  sc.r = take(kG);
-  sc.z = take(kG);
-  sc.n = take(kG);
-  sc.ghn = take(kG);
+  sc.gi = take(3 * G);
+  sc.hi = take(G);
+  sc.ho = take(G);
+  sc.r = take(G);
+  sc.z = take(G);
+  sc.n = take(G);
+  sc.ghn = take(G);
   sc.ya = take(kH);
   sc.yc = take(kH);
   sc.dl = take(kAPad);
   sc.dv = take(kAPad);
   sc.dya = take(kH);
   sc.dyc = take(kH);
-  sc.dho = take(kG);
-  sc.dgi = take(3 * kG);
-  sc.dgh = take(3 * kG);
+  sc.dho = take(G);
+  sc.dgi = take(3 * G);
+  sc.dgh = take(3 * G);
   sc.dx1 = take(kH);
   *out = h;
   return DPPO_OK;
@@ -771,6 +786,10 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
     set_error("invalid argument to dppo_gru_minibatch_grad_f32");
     return DPPO_EINVAL;
   }
+  if (h->dims.gru_hidden != kG && (uintptr_t)params % 16 != 0) {
+    set_error("dppo_gru_minibatch_grad_f32: params must be 16-byte aligned for gru_hidden > 16");
+    return DPPO_EINVAL;
+  }
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   static const bool attr = [] {
@@ -779,10 +798,10 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
   }();
   (void)attr;
   const dppo_gru_dims& d = h->dims;
-  int rc = launch_gru_grad(h->po, params, *batch, idx, m, h->wmask, h->B, d.rollout_steps,
-                           d.num_envs, d.obs_dim, d.act_dim, (float)(1.0 / (double)m_total),
-                           hp->ppo_clip, hp->value_loss_weight, hp->entropy_beta, h->sc, h->slabs,
-                           h->slab_stride, h->layout.total, s);
+  int rc = launch_gru_grad(d.gru_hidden, h->po, params, *batch, idx, m, h->wmask, h->B,
+                           d.rollout_steps, d.num_envs, d.obs_dim, d.act_dim,
+                           (float)(1.0 / (double)m_total), hp->ppo_clip, hp->value_loss_weight,
+                           hp->entropy_beta, h->sc, h->slabs, h->slab_stride, h->layout.total, s);
   if (rc != DPPO_OK) return rc;
   return launch_slab_reduce(h->slabs, h->G, h->slab_stride, h->layout.total, grad, h->sq_part,
                             LogStdTerm{-1, 0, 0.0f, 0}, s);
@@ -800,6 +819,9 @@ int dppo_gru_act_f32(dppo_gru_handle* h, const float* params, const dppo_gru_ste
   if (n == 0) return DPPO_OK;
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   GruTimed timed(h, 0);
+  if (h->dims.gru_hidden != kG)
+    return launch_gruw_act(h->dims.gru_hidden, h->po, params, *step, n, h->dims.obs_dim,
+                           h->dims.act_dim, seed, counter, (hipStream_t)stream);
   return launch_gru_act(h->po, params, *step, n, h->dims.obs_dim, h->dims.act_dim, seed, counter,
                         (hipStream_t)stream);
 }
@@ -815,8 +837,26 @@ int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs
   if (n == 0) return DPPO_OK;
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   GruTimed timed(h, 1);
+  if (h->dims.gru_hidden != kG)
+    return launch_gruw_value(h->dims.gru_hidden, h->po, params, obs, hx, dones, n,
+                             h->dims.obs_dim, values, (hipStream_t)stream);
   return launch_gru_value(h->po, params, obs, hx, dones, n, h->dims.obs_dim, values,
                           (hipStream_t)stream);
+}
+
+int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out) {
+  if (!out) {
+    set_error("out is NULL");
+    return DPPO_EINVAL;
+  }
+  const int rc = gru_validate(dims);
+  if (rc != DPPO_OK) return rc;
+  const int G = dims->gru_hidden;
+  out[0] = gru_envs(G);
+  out[1] = gru_grid(dims->num_envs, G);
+  out[2] = (int32_t)gru_lds_bytes(dims->obs_dim, G);
+  out[3] = G == kG ? 4 : gruw_act_envs();  // gruact.hip: one wave of 4 envs
+  return DPPO_OK;
 }
 
 int dppo_gru_set_timing(dppo_gru_handle* h, int32_t enable) {

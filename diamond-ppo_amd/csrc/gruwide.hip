@@ -1,0 +1,662 @@
+// RecurrentPPO minibatch gradient for GRU hidden widths 32 and 64: gru.hip's phases, scratch
+// contract and determinism contract on a mapping that scales with G.  (G = 16 stays on
+// gru_grad_kernel, whose per-thread gate arrays and register-resident Whh do not stretch: at
+// G = 64 they would be 192-float arrays, and the whole weight image would be 146 KB of LDS.)
+//
+// One workgroup = 256 / G envs over all T steps (256 threads): 8 envs at G = 32, 4 at G = 64, one
+// gradient slab each.  Phases as in gru.hip, separated by workgroup barriers and exchanging
+// per-sample vectors through the same global scratch (rows sized by G):
+//  A  per sample (thread per sample): x1, then gi = Wih x1 + bih in blocks of 48 gate rows;
+//  B  per env, serial in t: G lanes per env (lane j = hidden unit j, all in one wave), the
+//     recurrent half gh = Whh h + bhh and the cell; Whh read from LDS, h exchanged through LDS;
+//  C  per minibatch sample: heads, loss, head backward -> dL/dh' (h and dh' as G registers);
+//  D  per env, serial in reverse: BPTT through the cell, column j of Whh read from LDS;
+//  E  per sample: dx1 = (Wih^T dgi)(1 - x1^2), 64 accumulators, dgi streamed 4 rows at a time;
+//  F  weight gradients on v_mfma_f32_16x16x4_f32 (k = sample) in a fixed order, bias sums on
+//     VALU, one slab per workgroup.
+// No per-thread array is ever indexed by a run-time value.
+//
+// LDS holds the biases for the whole launch and, in one region restaged between the phases' own
+// barriers, only the weights the current phase reads: A Wb + Wih | B, D Whh | C Wa1 Wc1 Wa2 |
+// E Wih.  Whh is staged with a row stride of G + 1 floats: lane j's k-th read of its rows in B
+// ((gG + j)(G + 1) + k) and its column reads in D (g (G + 1) + j) both fall on 64 (or 2 x 32
+// pairwise equal) distinct consecutive banks.
+#include "common.h"
+
+namespace dppo {
+namespace {
+
+constexpr int kH = 64;     // MLP hidden
+constexpr int kThr = 256;
+constexpr int kAPad = 16;  // action dims padded
+constexpr int kGiBlk = 48; // gate rows per register block of phase A (= gru.hip's 3 G)
+
+struct GruwArgs {
+  GruOffsets po;
+  const float* params;
+  dppo_gru_batch b;
+  const float* wmask;  // [B] 1 for the minibatch's samples, else 0
+  int T, N, D, D16, A;
+  float inv_m, clip_eps, vf, ent;
+  GruScratch sc;
+  float* slabs;
+  int64_t slab_stride, p_total;
+};
+
+// LDS (floats): the phase's weights at W, then the biases, then the exchange buffers
+struct GruwLds {
+  int W, bb, bih, bhh, ba1, ba2, bc1, Wc2, bc2, hbuf, gbuf, red, total;
+};
+__host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
+__host__ __device__ constexpr GruwLds gruw_lds(int D, int G) {
+  GruwLds L{};
+  int o = 0;
+  L.W = o;
+  o += imax(imax(kH * D + 3 * G * kH, 3 * G * (G + 1)), 2 * kH * G + kAPad * kH);
+  o = (o + 3) & ~3;
+  L.bb = o; o += kH;
+  L.bih = o; o += 3 * G;
+  L.bhh = o; o += 3 * G;
+  L.ba1 = o; o += kH;
+  L.ba2 = o; o += kAPad;
+  L.bc1 = o; o += kH;
+  L.Wc2 = o; o += kH;
+  L.bc2 = o; o += 4;
+  L.hbuf = o; o += kThr;      // envs x G
+  L.gbuf = o; o += 3 * kThr;  // envs x 3 G
+  L.red = o; o += 3 * kThr;
+  L.total = o;
+  return L;
+}
+
+// n floats (a multiple of 4; both pointers 16-byte aligned) from global memory into LDS
+__device__ __forceinline__ void stage4(float* dst, const float* __restrict__ src, int n, int tid) {
+  for (int k = tid; k < n / 4; k += kThr) ((f32x4*)dst)[k] = ((const f32x4*)src)[k];
+}
+
+// Whh [3G][G] with a row stride of G + 1
+template <int G>
+__device__ __forceinline__ void stage_whh(float* dst, const float* __restrict__ src, int tid) {
+  for (int k = tid; k < 3 * G * G; k += kThr) dst[(k / G) * (G + 1) + (k % G)] = src[k];
+}
+
+// gru.hip's tile_sum: sum over k = samples of A[s][m] B[s][n] for one 16 x 16 output tile; s_k
+// enumerates the workgroup's samples (t, e) as t * N + n0 + e, e < ne, in t-major order.
+// The loads of kSumAhead k-steps are issued together (the loop is bound by their latency), the
+// MFMAs still chain in k order: the same bits as one step at a time.  NE > 0: ne == NE, a
+// compile-time divisor for the full workgroups.
+constexpr int kSumAhead = 8;
+template <int NE>
+__device__ __forceinline__ f32x4 tile_sum(const float* __restrict__ A, int lda, int mt,
+                                          const float* __restrict__ B, int ldb, int nt, int S,
+                                          int ne_, int N, int n0, int q, int r) {
+  const int ne = NE ? NE : ne_;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  int k0 = 0;
+  for (; k0 + 4 * kSumAhead <= S; k0 += 4 * kSumAhead) {
+    float av[kSumAhead], bv[kSumAhead];
+#pragma unroll
+    for (int u = 0; u < kSumAhead; ++u) {
+      const int s = k0 + 4 * u + q;
+      const int t = s / ne, e = s - t * ne;
+      const int64_t i = (int64_t)t * N + n0 + e;
+      av[u] = A[i * lda + 16 * mt + r];
+      bv[u] = B[i * ldb + 16 * nt + r];
+    }
+#pragma unroll
+    for (int u = 0; u < kSumAhead; ++u)
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+  }
+  for (; k0 < S; k0 += 4) {
+    const int s = k0 + q;
+    const bool ok = s < S;
+    const int ss = ok ? s : S - 1;
+    const int t = ss / ne, e = ss - t * ne;
+    const int64_t i = (int64_t)t * N + n0 + e;
+    const float a = ok ? A[i * lda + 16 * mt + r] : 0.0f;
+    const float b = B[i * ldb + 16 * nt + r];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+template <int G>
+__global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruwArgs a) {
+  constexpr int kEnvs = kThr / G, G3 = 3 * G, kWs = G + 1;
+  static_assert(G3 % kGiBlk == 0 && G3 <= kThr && G % 16 == 0, "gate blocking");
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const GruwLds L = gruw_lds(a.D, G);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = blockIdx.x * kEnvs;
+  const int ne = min(kEnvs, a.N - n0);
+  const int T = a.T, N = a.N, D = a.D, A = a.A;
+  const int S = T * ne;
+  const float* P = a.params;
+  const GruOffsets& po = a.po;
+  const GruScratch& sc = a.sc;
+  float* W = lds + L.W;
+
+  // ---- biases (and the critic's output row) for the whole launch; phase A's weights
+  if (tid < kH) {
+    lds[L.bb + tid] = P[po.bb + tid];
+    lds[L.ba1 + tid] = P[po.ba1 + tid];
+    lds[L.bc1 + tid] = P[po.bc1 + tid];
+    lds[L.Wc2 + tid] = P[po.Wc2 + tid];
+  }
+  if (tid < G3) {
+    lds[L.bih + tid] = P[po.bih + tid];
+    lds[L.bhh + tid] = P[po.bhh + tid];
+  }
+  if (tid < kAPad) lds[L.ba2 + tid] = tid < A ? P[po.ba2 + tid] : 0.f;
+  if (tid == 0) lds[L.bc2] = P[po.bc2];
+  float* Wb = W;
+  float* Wih = W + kH * D;
+  stage4(Wb, P + po.Wb, kH * D, tid);
+  stage4(Wih, P + po.Wih, G3 * kH, tid);
+  __syncthreads();
+
+  // ---- A: x1 (8 features at a time, as gru.hip), then gi in blocks of kGiBlk gate rows with
+  // x1 re-read from the scratch row this thread just wrote
+  for (int s = tid; s < S; s += kThr) {
+    const int t = s / ne, e = s - t * ne;
+    const int64_t i = (int64_t)t * N + n0 + e;
+    {
+      float ob[32];
+#pragma unroll
+      for (int c = 0; c < 32; ++c) ob[c] = c < D ? a.b.obs[i * D + c] : 0.f;
+      float* ob16 = sc.obs + i * a.D16;
+#pragma unroll
+      for (int c = 0; c < 32; ++c)
+        if (c < a.D16) ob16[c] = ob[c];
+#pragma unroll 1
+      for (int o0 = 0; o0 < kH; o0 += 8) {
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          float z = lds[L.bb + o0 + u];
+#pragma unroll
+          for (int c = 0; c < 32; ++c)
+            if (c < D) z += Wb[(o0 + u) * D + c] * ob[c];
+          x[u] = tanh_acc(z);
+        }
+        f32x4* xo = (f32x4*)(sc.x1 + i * kH + o0);
+        xo[0] = (f32x4){x[0], x[1], x[2], x[3]};
+        xo[1] = (f32x4){x[4], x[5], x[6], x[7]};
+      }
+    }
+#pragma unroll 1
+    for (int g0 = 0; g0 < G3; g0 += kGiBlk) {
+      float gi[kGiBlk];
+#pragma unroll
+      for (int g = 0; g < kGiBlk; ++g) gi[g] = lds[L.bih + g0 + g];
+      const float* wrow = Wih + g0 * kH;
+#pragma unroll 1
+      for (int o0 = 0; o0 < kH; o0 += 8) {
+        const f32x4 xa = *(const f32x4*)(sc.x1 + i * kH + o0);
+        const f32x4 xb = *(const f32x4*)(sc.x1 + i * kH + o0 + 4);
+#pragma unroll
+        for (int g = 0; g < kGiBlk; ++g) {
+          const f32x4 w0 = *(const f32x4*)(wrow + g * kH + o0);
+          const f32x4 w1 = *(const f32x4*)(wrow + g * kH + o0 + 4);
+          gi[g] += ((w0[0] * xa[0] + w0[1] * xa[1]) + (w0[2] * xa[2] + w0[3] * xa[3])) +
+                   ((w1[0] * xb[0] + w1[1] * xb[1]) + (w1[2] * xb[2] + w1[3] * xb[3]));
+        }
+      }
+      f32x4* go = (f32x4*)(sc.gi + i * G3 + g0);
+#pragma unroll
+      for (int g = 0; g < kGiBlk / 4; ++g)
+        go[g] = (f32x4){gi[4 * g], gi[4 * g + 1], gi[4 * g + 2], gi[4 * g + 3]};
+    }
+  }
+  __syncthreads();
+  stage_whh<G>(W, P + po.Whh, tid);
+  __syncthreads();
+
+  // ---- B: forward recurrence, lane j of env e = hidden unit j (G lanes of one wave per env)
+  const int e = tid / G, j = tid % G;
+  const bool env_ok = e < ne;
+  const int n = n0 + e;
+  if (env_ok) {
+    const float* wr = W + j * kWs;
+    const float* wz = W + (G + j) * kWs;
+    const float* wn = W + (2 * G + j) * kWs;
+    const float br = lds[L.bhh + j], bz = lds[L.bhh + G + j], bn = lds[L.bhh + 2 * G + j];
+    float h = a.b.hx0[(int64_t)n * G + j];
+    float* hb = lds + L.hbuf + e * G;
+    // the next step's inputs are loaded a step ahead (they do not depend on h)
+    float gir_n = sc.gi[(int64_t)n * G3 + j], giz_n = sc.gi[(int64_t)n * G3 + G + j],
+          gin_n = sc.gi[(int64_t)n * G3 + 2 * G + j];
+    uint8_t done_n = a.b.prev_dones[n];
+    for (int t = 0; t < T; ++t) {
+      const int64_t i = (int64_t)t * N + n;
+      const float gir = gir_n, giz = giz_n, gin = gin_n;
+      const bool done = done_n;
+      {
+        const int64_t in = (int64_t)min(t + 1, T - 1) * N + n;
+        gir_n = sc.gi[in * G3 + j];
+        giz_n = sc.gi[in * G3 + G + j];
+        gin_n = sc.gi[in * G3 + 2 * G + j];
+        done_n = a.b.prev_dones[in];
+      }
+      if (done) h = 0.0f;  // hx[:, dones[t]] = 0 (recurrent_ppo.py:84)
+      hb[j] = h;
+      float ghr = br, ghz = bz, ghn = bn;
+#pragma unroll
+      for (int q = 0; q < G / 4; ++q) {
+        const f32x4 x = *(const f32x4*)(hb + 4 * q);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          ghr += wr[4 * q + u] * x[u];
+          ghz += wz[4 * q + u] * x[u];
+          ghn += wn[4 * q + u] * x[u];
+        }
+      }
+      const float r = sigm(gir + ghr), z = sigm(giz + ghz);
+      const float nn = tanh_acc(gin + r * ghn);
+      const float hn = (1.0f - z) * nn + z * h;
+      sc.hi[i * G + j] = h;
+      sc.r[i * G + j] = r;
+      sc.z[i * G + j] = z;
+      sc.n[i * G + j] = nn;
+      sc.ghn[i * G + j] = ghn;
+      sc.ho[i * G + j] = hn;
+      h = hn;
+    }
+  }
+  __syncthreads();
+  float* Wa1 = W;
+  float* Wc1 = W + kH * G;
+  float* Wa2 = W + 2 * kH * G;
+  stage4(Wa1, P + po.Wa1, kH * G, tid);
+  stage4(Wc1, P + po.Wc1, kH * G, tid);
+  for (int k = tid; k < kAPad * kH; k += kThr) Wa2[k] = (k >> 6) < A ? P[po.Wa2 + k] : 0.f;
+  __syncthreads();
+
+  // ---- C: heads, loss and head backward per sample (ppo.py:264-280 with the GRU features):
+  // gru.hip's phase C with the feature dots running over G
+  float s_pi = 0.f, s_v = 0.f, s_ent = 0.f;
+  for (int s = tid; s < S; s += kThr) {
+    const int t = s / ne, ee = s - t * ne;
+    const int64_t i = (int64_t)t * N + n0 + ee;
+    const float w = a.wmask[i];
+    float dl[kAPad];
+    float dv = 0.f;
+#pragma unroll
+    for (int k = 0; k < kAPad; ++k) dl[k] = 0.f;
+    float* yar = sc.ya + i * kH;
+    float* ycr = sc.yc + i * kH;
+    float* dyar = sc.dya + i * kH;
+    float* dycr = sc.dyc + i * kH;
+    f32x4* dhor = (f32x4*)(sc.dho + i * G);
+    if (w != 0.f) {
+      float out[kAPad];
+#pragma unroll
+      for (int k = 0; k < kAPad; ++k) out[k] = lds[L.ba2 + k];
+      float val = lds[L.bc2];
+      {
+        float hv[G];
+#pragma unroll
+        for (int q = 0; q < G / 4; ++q) {
+          const f32x4 x = ((const f32x4*)(sc.ho + i * G))[q];
+          hv[4 * q] = x[0];
+          hv[4 * q + 1] = x[1];
+          hv[4 * q + 2] = x[2];
+          hv[4 * q + 3] = x[3];
+        }
+#pragma unroll 1
+        for (int o0 = 0; o0 < kH; o0 += 8) {
+          float ya[8], yc[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            float za = lds[L.ba1 + o0 + u], zc = lds[L.bc1 + o0 + u];
+#pragma unroll
+            for (int q = 0; q < G / 4; ++q) {
+              const f32x4 wa = *(const f32x4*)(Wa1 + (o0 + u) * G + 4 * q);
+              const f32x4 wc = *(const f32x4*)(Wc1 + (o0 + u) * G + 4 * q);
+              za += (wa[0] * hv[4 * q] + wa[1] * hv[4 * q + 1]) + (wa[2] * hv[4 * q + 2] + wa[3] * hv[4 * q + 3]);
+              zc += (wc[0] * hv[4 * q] + wc[1] * hv[4 * q + 1]) + (wc[2] * hv[4 * q + 2] + wc[3] * hv[4 * q + 3]);
+            }
+            ya[u] = tanh_acc(za);
+            yc[u] = tanh_acc(zc);
+          }
+          ((f32x4*)(yar + o0))[0] = (f32x4){ya[0], ya[1], ya[2], ya[3]};
+          ((f32x4*)(yar + o0))[1] = (f32x4){ya[4], ya[5], ya[6], ya[7]};
+          ((f32x4*)(ycr + o0))[0] = (f32x4){yc[0], yc[1], yc[2], yc[3]};
+          ((f32x4*)(ycr + o0))[1] = (f32x4){yc[4], yc[5], yc[6], yc[7]};
+#pragma unroll
+          for (int k = 0; k < kAPad; ++k) {
+            if (k < A) {
+              const f32x4 w0 = *(const f32x4*)(Wa2 + k * kH + o0);
+              const f32x4 w1 = *(const f32x4*)(Wa2 + k * kH + o0 + 4);
+              out[k] += ((w0[0] * ya[0] + w0[1] * ya[1]) + (w0[2] * ya[2] + w0[3] * ya[3])) +
+                        ((w1[0] * ya[4] + w1[1] * ya[5]) + (w1[2] * ya[6] + w1[3] * ya[7]));
+            }
+          }
+          const f32x4 v0 = *(const f32x4*)(lds + L.Wc2 + o0);
+          const f32x4 v1 = *(const f32x4*)(lds + L.Wc2 + o0 + 4);
+          val += ((v0[0] * yc[0] + v0[1] * yc[1]) + (v0[2] * yc[2] + v0[3] * yc[3])) +
+                 ((v1[0] * yc[4] + v1[1] * yc[5]) + (v1[2] * yc[6] + v1[3] * yc[7]));
+        }
+      }
+      const int act = a.b.actions[i];
+      float mx = out[0];
+#pragma unroll
+      for (int k = 1; k < kAPad; ++k)
+        if (k < A) mx = fmaxf(mx, out[k]);
+      float se = 0.f;
+#pragma unroll
+      for (int k = 0; k < kAPad; ++k)
+        if (k < A) se += __expf(out[k] - mx);
+      const float lse = mx + __logf(se);
+      float ent = 0.f, logp = 0.f;
+#pragma unroll
+      for (int k = 0; k < kAPad; ++k) {
+        const float lpk = out[k] - lse;
+        const float pk = k < A ? __expf(lpk) : 0.f;
+        ent -= pk * lpk;
+        logp = k == act ? lpk : logp;
+        out[k] = lpk;  // log-probabilities from here on
+      }
+      const float adv = a.b.advantages[i], ret = a.b.returns[i];
+      const float ratio = __expf(logp - a.b.old_log_probs[i]);                 // ppo.py:266
+      const float rcl = fminf(fmaxf(ratio, 1.0f - a.clip_eps), 1.0f + a.clip_eps);
+      const float u = -adv * ratio, wv = -adv * rcl;                            // ppo.py:267-269
+      const float inr = (ratio >= 1.0f - a.clip_eps && ratio <= 1.0f + a.clip_eps) ? 1.f : 0.f;
+      const float gu = u > wv ? 1.f : (u == wv ? 0.5f : 0.f);  // torch.max splits ties
+      const float gw = wv > u ? 1.f : (u == wv ? 0.5f : 0.f);
+      const float vm = w * a.inv_m;
+      const float dlogp = (gu * -adv + gw * -adv * inr) * vm * ratio;
+      dv = a.vf * (val - ret) * vm;                                            // ppo.py:272
+      s_pi += fmaxf(u, wv);
+      s_v += 0.5f * (val - ret) * (val - ret);
+      s_ent += ent;
+#pragma unroll
+      for (int k = 0; k < kAPad; ++k) {
+        const float pk = k < A ? __expf(out[k]) : 0.f;
+        dl[k] = k < A ? dlogp * ((k == act ? 1.f : 0.f) - pk) + a.ent * vm * pk * (out[k] + ent)
+                      : 0.f;
+      }
+      // head backward: dya = (Wa2^T dl)(1 - ya^2), dyc = Wc2 dv (1 - yc^2),
+      // dh' = Wa1^T dya + Wc1^T dyc
+      float dho[G];
+#pragma unroll
+      for (int k = 0; k < G; ++k) dho[k] = 0.f;
+#pragma unroll 1
+      for (int o0 = 0; o0 < kH; o0 += 4) {
+        const f32x4 ya = *(const f32x4*)(yar + o0);
+        const f32x4 yc = *(const f32x4*)(ycr + o0);
+        f32x4 da = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < kAPad; ++k)
+          if (k < A) da += *(const f32x4*)(Wa2 + k * kH + o0) * dl[k];
+        const f32x4 dya = da * (1.0f - ya * ya);
+        const f32x4 dyc = *(const f32x4*)(lds + L.Wc2 + o0) * dv * (1.0f - yc * yc);
+        *(f32x4*)(dyar + o0) = dya;
+        *(f32x4*)(dycr + o0) = dyc;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+          for (int q = 0; q < G / 4; ++q) {
+            const f32x4 wa = *(const f32x4*)(Wa1 + (o0 + u) * G + 4 * q);
+            const f32x4 wc = *(const f32x4*)(Wc1 + (o0 + u) * G + 4 * q);
+#pragma unroll
+            for (int x = 0; x < 4; ++x) dho[4 * q + x] += wa[x] * dya[u] + wc[x] * dyc[u];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < G / 4; ++k)
+        dhor[k] = (f32x4){dho[4 * k], dho[4 * k + 1], dho[4 * k + 2], dho[4 * k + 3]};
+    } else {
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int o = 0; o < kH / 4; ++o) {
+        ((f32x4*)yar)[o] = zero;
+        ((f32x4*)ycr)[o] = zero;
+        ((f32x4*)dyar)[o] = zero;
+        ((f32x4*)dycr)[o] = zero;
+      }
+#pragma unroll
+      for (int k = 0; k < G / 4; ++k) dhor[k] = zero;
+    }
+#pragma unroll
+    for (int k = 0; k < kAPad / 4; ++k)
+      ((f32x4*)(sc.dl + i * kAPad))[k] = (f32x4){dl[4 * k], dl[4 * k + 1], dl[4 * k + 2], dl[4 * k + 3]};
+    ((f32x4*)(sc.dv + i * kAPad))[0] = (f32x4){dv, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 1; k < kAPad / 4; ++k) ((f32x4*)(sc.dv + i * kAPad))[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  __syncthreads();
+  stage_whh<G>(W, P + po.Whh, tid);
+  __syncthreads();
+
+  // ---- D: BPTT, reverse in t (lane j of env e reads column j of Whh)
+  if (env_ok) {
+    const float* wc = W + j;
+    float* gb = lds + L.gbuf + e * G3;
+    float carry = 0.0f;
+    // the earlier step's saved activations are loaded a step ahead (they do not depend on carry)
+    struct Saved {
+      float dho, z, n, r, hi, ghn;
+      uint8_t done;
+    };
+    auto load = [&](int t) {
+      const int64_t i = (int64_t)t * N + n;
+      return Saved{sc.dho[i * G + j], sc.z[i * G + j], sc.n[i * G + j], sc.r[i * G + j],
+                   sc.hi[i * G + j], sc.ghn[i * G + j], a.b.prev_dones[i]};
+    };
+    Saved nx = load(T - 1);
+    for (int t = T - 1; t >= 0; --t) {
+      const int64_t i = (int64_t)t * N + n;
+      const Saved cur = nx;
+      nx = load(max(t - 1, 0));
+      const float dh = cur.dho + carry;
+      const float z = cur.z, nn = cur.n, r = cur.r;
+      const float hin = cur.hi, ghn = cur.ghn;
+      const float dn = dh * (1.0f - z);
+      const float dz = dh * (hin - nn);
+      const float dnp = dn * (1.0f - nn * nn);
+      const float dghn = dnp * r;
+      const float drp = dnp * ghn * r * (1.0f - r);
+      const float dzp = dz * z * (1.0f - z);
+      float* dgi = sc.dgi + i * G3;
+      float* dgh = sc.dgh + i * G3;
+      dgi[j] = drp;
+      dgi[G + j] = dzp;
+      dgi[2 * G + j] = dnp;
+      dgh[j] = drp;
+      dgh[G + j] = dzp;
+      dgh[2 * G + j] = dghn;
+      gb[j] = drp;
+      gb[G + j] = dzp;
+      gb[2 * G + j] = dghn;
+      float dhin = dh * z;
+#pragma unroll
+      for (int q = 0; q < G3 / 4; ++q) {
+        const f32x4 x = *(const f32x4*)(gb + 4 * q);
+        dhin += wc[(4 * q) * kWs] * x[0] + wc[(4 * q + 1) * kWs] * x[1] +
+                wc[(4 * q + 2) * kWs] * x[2] + wc[(4 * q + 3) * kWs] * x[3];
+      }
+      // h_in = h_prev * keep  =>  dh_prev = dh_in * keep
+      carry = cur.done ? 0.0f : dhin;
+    }
+  }
+  __syncthreads();
+  stage4(W, P + po.Wih, G3 * kH, tid);
+  __syncthreads();
+
+  // ---- E: dx1 = (Wih^T dgi)(1 - x1^2) per sample: all 64 features accumulate in registers
+  // while the sample's dgi streams through four gate rows at a time
+  for (int s = tid; s < S; s += kThr) {
+    const int t = s / ne, ee = s - t * ne;
+    const int64_t i = (int64_t)t * N + n0 + ee;
+    f32x4 d[kH / 4];
+#pragma unroll
+    for (int c = 0; c < kH / 4; ++c) d[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const f32x4* dgr = (const f32x4*)(sc.dgi + i * G3);
+#pragma unroll 1
+    for (int g0 = 0; g0 < G3; g0 += 4) {
+      const f32x4 dg = dgr[g0 / 4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int c = 0; c < kH / 4; ++c) d[c] += *(const f32x4*)(W + (g0 + u) * kH + 4 * c) * dg[u];
+      }
+    }
+    const f32x4* x1 = (const f32x4*)(sc.x1 + i * kH);
+    f32x4* dx = (f32x4*)(sc.dx1 + i * kH);
+#pragma unroll
+    for (int c = 0; c < kH / 4; ++c) {
+      const f32x4 x = x1[c];
+      dx[c] = d[c] * (1.0f - x * x);
+    }
+  }
+  __syncthreads();
+
+  // ---- F: weight gradients (MFMA over samples), biases and loss sums into this workgroup's slab
+  float* slab = a.slabs + (int64_t)blockIdx.x * a.slab_stride;
+  {
+    const int q = lane >> 4, r = lane & 15;
+    const int nD = a.D16 / 16;
+    constexpr int nG = G / 16, nG3 = G3 / 16;
+    // tiles: Wb 4 x nD | Wih 3G/16 x 4 | Whh 3G/16 x G/16 | Wa1 4 x G/16 | Wc1 4 x G/16 |
+    //        Wa2 1 x 4 | Wc2 1 x 4
+    const int nt_b = 4 * nD, nt_ih = nG3 * 4, nt_hh = nG3 * nG, nt_a1 = 4 * nG, nt_c1 = 4 * nG,
+              nt_a2 = 4, nt_c2 = 4;
+    const int ntiles = nt_b + nt_ih + nt_hh + nt_a1 + nt_c1 + nt_a2 + nt_c2;
+    for (int tl = wave; tl < ntiles; tl += kThr / 64) {
+      int k = tl;
+      const float *Aa, *Bb;
+      int lda, ldb, mt, nt, rows, cols, ldo;
+      int64_t off;
+      if (k < nt_b) {
+        Aa = sc.dx1; lda = kH; Bb = sc.obs; ldb = a.D16; mt = k / nD; nt = k % nD;
+        off = po.Wb; rows = kH; cols = D; ldo = D;
+      } else if ((k -= nt_b) < nt_ih) {
+        Aa = sc.dgi; lda = G3; Bb = sc.x1; ldb = kH; mt = k / 4; nt = k % 4;
+        off = po.Wih; rows = G3; cols = kH; ldo = kH;
+      } else if ((k -= nt_ih) < nt_hh) {
+        Aa = sc.dgh; lda = G3; Bb = sc.hi; ldb = G; mt = k / nG; nt = k % nG;
+        off = po.Whh; rows = G3; cols = G; ldo = G;
+      } else if ((k -= nt_hh) < nt_a1) {
+        Aa = sc.dya; lda = kH; Bb = sc.ho; ldb = G; mt = k / nG; nt = k % nG;
+        off = po.Wa1; rows = kH; cols = G; ldo = G;
+      } else if ((k -= nt_a1) < nt_c1) {
+        Aa = sc.dyc; lda = kH; Bb = sc.ho; ldb = G; mt = k / nG; nt = k % nG;
+        off = po.Wc1; rows = kH; cols = G; ldo = G;
+      } else if ((k -= nt_c1) < nt_a2) {
+        Aa = sc.dl; lda = kAPad; Bb = sc.ya; ldb = kH; mt = 0; nt = k;
+        off = po.Wa2; rows = A; cols = kH; ldo = kH;
+      } else {
+        k -= nt_a2;
+        Aa = sc.dv; lda = kAPad; Bb = sc.yc; ldb = kH; mt = 0; nt = k;
+        off = po.Wc2; rows = 1; cols = kH; ldo = kH;
+      }
+      const f32x4 acc = ne == kEnvs ? tile_sum<kEnvs>(Aa, lda, mt, Bb, ldb, nt, S, ne, N, n0, q, r)
+                                    : tile_sum<0>(Aa, lda, mt, Bb, ldb, nt, S, ne, N, n0, q, r);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int row = 16 * mt + 4 * q + v, col = 16 * nt + r;
+        if (row < rows && col < cols) slab[off + (int64_t)row * ldo + col] = acc[v];
+      }
+    }
+  }
+  {
+    // bias columns: bb 64 | bih 3G | bhh 3G | ba1 64 | bc1 64 | ba2 A | bc2 1
+    const int nb = kH + G3 + G3 + kH + kH + A + 1;
+    for (int c = tid; c < nb; c += kThr) {
+      const float* src;
+      int ld, col;
+      int64_t off;
+      int k = c;
+      if (k < kH) { src = sc.dx1; ld = kH; col = k; off = po.bb + k; }
+      else if ((k -= kH) < G3) { src = sc.dgi; ld = G3; col = k; off = po.bih + k; }
+      else if ((k -= G3) < G3) { src = sc.dgh; ld = G3; col = k; off = po.bhh + k; }
+      else if ((k -= G3) < kH) { src = sc.dya; ld = kH; col = k; off = po.ba1 + k; }
+      else if ((k -= kH) < kH) { src = sc.dyc; ld = kH; col = k; off = po.bc1 + k; }
+      else if ((k -= kH) < A) { src = sc.dl; ld = kAPad; col = k; off = po.ba2 + k; }
+      else { src = sc.dv; ld = kAPad; col = 0; off = po.bc2; }
+      // sample order s = 0, 1, ...; the loads of kSumAhead samples in flight together
+      float sum = 0.f;
+      int s = 0;
+      for (; s + kSumAhead <= S; s += kSumAhead) {
+        float v[kSumAhead];
+#pragma unroll
+        for (int u = 0; u < kSumAhead; ++u) {
+          const int t = (s + u) / ne, ee = (s + u) - t * ne;
+          v[u] = src[((int64_t)t * N + n0 + ee) * ld + col];
+        }
+#pragma unroll
+        for (int u = 0; u < kSumAhead; ++u) sum += v[u];
+      }
+      for (; s < S; ++s) {
+        const int t = s / ne, ee = s - t * ne;
+        sum += src[((int64_t)t * N + n0 + ee) * ld + col];
+      }
+      slab[off] = sum;
+    }
+  }
+  // loss sums {policy, value, entropy} in a fixed order
+  float* red = lds + L.red;
+  red[tid] = s_pi;
+  red[kThr + tid] = s_v;
+  red[2 * kThr + tid] = s_ent;
+  __syncthreads();
+  if (tid < 3) {
+    float sum = 0.f;
+    for (int k = 0; k < kThr; ++k) sum += red[tid * kThr + k];
+    slab[a.p_total + tid] = sum;
+  }
+}
+
+template <int G>
+int launch_g(const GruwArgs& a, hipStream_t s) {
+  static const bool attr = [] {
+    raise_dyn_lds((const void*)gruw_grad_kernel<G>);
+    return true;
+  }();
+  (void)attr;
+  const size_t lds = (size_t)gruw_lds(a.D, G).total * sizeof(float);
+  const int grid = (a.N + kThr / G - 1) / (kThr / G);
+  DPPO_LAUNCH(gruw_grad_kernel<G>, dim3(grid), dim3(kThr), lds, s, a);
+  DPPO_LAUNCH_CHECK();
+  return DPPO_OK;
+}
+
+}  // namespace
+
+bool gruw_width(int G) { return G == 32 || G == 64; }
+
+int gruw_envs(int G) { return kThr / G; }
+
+size_t gruw_lds_bytes(int D, int G) { return (size_t)gruw_lds(D, G).total * sizeof(float); }
+
+int launch_gruw_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
+                     const float* wmask, int T, int N, int D, int A, float inv_m, float clip_eps,
+                     float vf, float ent, const GruScratch& sc, float* slabs, int64_t slab_stride,
+                     int64_t p_total, hipStream_t s) {
+  GruwArgs a{};
+  a.po = po;
+  a.params = params;
+  a.b = b;
+  a.wmask = wmask;
+  a.T = T;
+  a.N = N;
+  a.D = D;
+  a.D16 = (D + 15) / 16 * 16;
+  a.A = A;
+  a.inv_m = inv_m;
+  a.clip_eps = clip_eps;
+  a.vf = vf;
+  a.ent = ent;
+  a.sc = sc;
+  a.slabs = slabs;
+  a.slab_stride = slab_stride;
+  a.p_total = p_total;
+  if (G == 32) return launch_g<32>(a, s);
+  if (G == 64) return launch_g<64>(a, s);
+  set_error("no wide GRU gradient kernel for gru_hidden=%d", G);
+  return DPPO_EUNSUPPORTED;
+}
+
+}  // namespace dppo

@@ -38,6 +38,7 @@ EXPORTED = [
     "dppo_peer_selftest",
     "dppo_gru_param_layout", "dppo_gru_create", "dppo_gru_destroy", "dppo_gru_minibatch_grad_f32",
     "dppo_gru_act_f32", "dppo_gru_value_f32", "dppo_gru_set_timing", "dppo_gru_get_timing",
+    "dppo_gru_plan",
 ]
 TIMING_CLASSES = ["eval", "gae", "adv_stats", "pack", "grad", "slab_reduce", "clip_adam",
                   "allreduce", "perm", "reduce_adam", "gae_probe"]
@@ -179,6 +180,7 @@ def load():
         "dppo_gru_act_f32": (ctypes.c_int, [vp, vp, P(GruStep), i64, ctypes.c_uint64,
                                             ctypes.c_uint64, vp]),
         "dppo_gru_value_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, vp, vp]),
+        "dppo_gru_plan": (ctypes.c_int, [P(GruDims), vp]),
         "dppo_gru_set_timing": (ctypes.c_int, [vp, i32]),
         "dppo_gru_get_timing": (ctypes.c_int, [vp, vp, vp]),
         "dppo_set_timing": (ctypes.c_int, [vp, i32]),

@@ -21,6 +21,7 @@ is its local mean scaled by 1/world, and the flat gradient is all-reduced (SUM, 
 from __future__ import annotations
 
 import ctypes
+import os
 import time
 from dataclasses import dataclass
 from math import sqrt
@@ -121,6 +122,18 @@ def network_parameter_init_(network: nn.Module, gain: float = 1.0) -> None:
             nn.init.orthogonal_(network.actor_out_layer.weight, gain=0.01)
 
 
+def fused_gru_shape(hidden: int, gru_hidden: int, obs_dim: int, act_dim: int) -> bool:
+    """Whether the fused GRU kernels (``fused_gru``, ``fused_rollout``) serve the default network
+    at this shape: hidden 64, gru_hidden 16, 32 or 64, obs_dim <= 32, act_dim <= 16.  The same
+    predicate as ``gru_validate`` (csrc/gru.hip).  ``DPPO_GRU_WIDE=0`` turns gru_hidden 32 and 64
+    off (A/B runs against the torch path); 16 is not affected."""
+    if not (hidden == 64 and 1 <= obs_dim <= 32 and 1 <= act_dim <= 16):
+        return False
+    if gru_hidden == 16:
+        return True
+    return gru_hidden in (32, 64) and os.environ.get("DPPO_GRU_WIDE", "1") != "0"
+
+
 class RecurrentPPO:
     # learn() runs each minibatch's sequence recompute, loss and BPTT as one fused HIP launch
     # (dppo_gru_minibatch_grad_f32) for the default network at supported shapes; False (or any
@@ -158,10 +171,12 @@ class RecurrentPPO:
         self.handle = N.Handle(self.device.index or 0, dims)
         self.gru = None
         obs_dim = int(np.prod(obs_space.shape))
-        if (type(self.network) is RecurrentActorCriticNetwork and cfg.network_hidden_dim == 64
-                and cfg.gru_hidden_dim == 16 and obs_dim <= 32 and int(act_space.n) <= 16):
+        if (type(self.network) is RecurrentActorCriticNetwork
+                and fused_gru_shape(cfg.network_hidden_dim, cfg.gru_hidden_dim, obs_dim,
+                                    int(act_space.n))):
             gd = N.GruDims(rollout_steps=cfg.rollout_steps, num_envs=cfg.num_envs,
-                           obs_dim=obs_dim, act_dim=int(act_space.n), hidden=64, gru_hidden=16)
+                           obs_dim=obs_dim, act_dim=int(act_space.n), hidden=64,
+                           gru_hidden=cfg.gru_hidden_dim)
             self.gru = N.GruHandle(self.device.index or 0, gd)
             L = self.gru.layout
             if L.total != self.flat.total or any(L.offset[i] != o for i, o in

@@ -436,7 +436,7 @@ typedef struct dppo_gru_dims {
   int32_t obs_dim;       /* D <= 32 */
   int32_t act_dim;       /* discrete actions A <= 16 */
   int32_t hidden;        /* network_hidden_dim, must be 64 */
-  int32_t gru_hidden;    /* gru_hidden_dim, must be 16 */
+  int32_t gru_hidden;    /* gru_hidden_dim G: 16, 32 or 64 */
 } dppo_gru_dims;
 
 /* One rollout as RecurrentPPO.learn stacks it (recurrent_ppo.py:306-316), device pointers. */
@@ -455,12 +455,18 @@ typedef struct dppo_gru_batch {
 int dppo_gru_param_layout(const dppo_gru_dims* dims, dppo_layout* out);
 int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out);
 void dppo_gru_destroy(dppo_gru_handle* h);
+/* How the kernels map a supported shape (no device needed): out[0] envs per workgroup of the
+ * minibatch kernel, out[1] its workgroups (= gradient slabs) for dims->num_envs, out[2] its LDS
+ * bytes, out[3] envs per workgroup of the two rollout kernels.  DPPO_EUNSUPPORTED as
+ * dppo_gru_create. */
+int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out);
 
 /* One minibatch gradient of the recurrent PPO loss (recurrent_ppo.py:335-360): the GRU sequence
  * over all T x N samples from hx0, the clipped-surrogate + value + entropy loss on the m samples
  * idx[0..m) (flat t * N + n), divided by m_total (the global minibatch size), and the analytic
  * backward through time.  grad [layout.total + 8]: the summed gradient in the flat layout, then
- * the loss sums {policy, value, entropy} (divide by m_total).  Stream-ordered, deterministic. */
+ * the loss sums {policy, value, entropy} (divide by m_total).  Stream-ordered, deterministic.
+ * For gru_hidden > 16 params must be 16-byte aligned. */
 int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
                                 const dppo_gru_batch* batch, const int32_t* idx, int32_t m,
                                 int32_t m_total, const dppo_hparams* hp, float* grad,
@@ -470,8 +476,8 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
 typedef struct dppo_gru_step {
   const float* obs;          /* [n][D] */
   const uint8_t* prev_dones; /* [n], hidden state zeroed before the step where set (:84) */
-  const float* hx;           /* [n][16] hidden state before the step */
-  float* hx_out;             /* [n][16] after the step; must not alias hx */
+  const float* hx;           /* [n][G] hidden state before the step */
+  float* hx_out;             /* [n][G] after the step; must not alias hx */
   int32_t* actions;          /* [n] sampled action */
   float* log_probs;          /* [n] log-prob of the sampled action */
   float* values;             /* [n] */
@@ -491,7 +497,7 @@ int dppo_gru_act_f32(dppo_gru_handle* h, const float* params, const dppo_gru_ste
                      int64_t n, uint64_t seed, uint64_t counter, void* stream);
 
 /* V(next_obs) after the step (replaces get_values, recurrent_ppo.py:226-232): base layer, one
- * GRU step from hx [n][16] (zeroed first where dones is set; dones may be NULL) and the critic
+ * GRU step from hx [n][G] (zeroed first where dones is set; dones may be NULL) and the critic
  * head -> values [n].  The new hidden state is discarded, as in the reference.  Stream-ordered,
  * allocates nothing. */
 int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs,

@@ -1,0 +1,257 @@
+"""RecurrentPPO's fused rollout step at gru_hidden_dim 32 and 64 (csrc/gruactwide.hip behind
+dppo_gru_act_f32 / dppo_gru_value_f32) and the rollout() path on it: tests/test_gpu_gru_act.py's
+checks with the same yardstick (the float64 CPU module), the same bounds (atol 2e-5, rtol 1e-5)
+and the same NumPy restatement of the Philox stream, which must not depend on G."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import diamond
+from diamond import _native as N
+from oracle import gru_torch as GT
+
+from test_gpu_gru_act import (ATOL, M32, RTOL, _dev, _oracle_net, _start, log_softmax64,
+                              oracle_step, oracle_value, run_value)
+from test_gpu_rollout_ckpt import philox4x32_10, u01
+
+WIDTHS = (32, 64)
+ENVS_PER_WG = 4     # both widths (dppo_gru_plan out[3], checked below)
+
+_agents = {}
+
+
+def _agent(G, D, A, T=2, Nn=4, spread=True, cache=True, **kw):
+    import gym_stub
+    key = (G, D, A, T, Nn, spread)
+    if cache and not kw and key in _agents:
+        return _agents[key]
+    np.random.seed(0)
+    torch.manual_seed(0)
+    envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
+    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
+                                     gru_hidden_dim=G, **kw)
+    agent = diamond.RecurrentPPO(None, cfg, envs=envs)
+    assert agent.gru is not None, "gru_hidden_dim %d did not take the fused path" % G
+    if spread:   # spread the weights so gates and heads leave their linear range
+        torch.manual_seed(1)
+        with torch.no_grad():
+            for p in agent.network.parameters():
+                p.add_(torch.randn_like(p) * 0.3)
+    if cache and not kw:
+        _agents[key] = agent
+    return agent
+
+
+def _inputs(n, D, G, seed, done_frac=0.3):
+    rng = np.random.default_rng(seed)
+    return (rng.standard_normal((n, D)).astype(np.float32),
+            rng.random(n) < done_frac,
+            (rng.standard_normal((n, G)) * 0.5).astype(np.float32))
+
+
+def run_act(agent, obs, dones, hx, seed=1, counter=0, logits=True):
+    """One dppo_gru_act_f32 call on host arrays -> dict of host arrays."""
+    n, A, G, dev = obs.shape[0], agent.gru.dims.act_dim, agent.gru.dims.gru_hidden, agent.device
+    o, d, h = _dev(agent, obs), _dev(agent, dones, torch.uint8), _dev(agent, hx)
+    out = dict(hx_out=torch.empty((n, G), device=dev),
+               actions=torch.empty(n, dtype=torch.int32, device=dev),
+               log_probs=torch.empty(n, device=dev), values=torch.empty(n, device=dev),
+               logits=torch.empty((n, A), device=dev) if logits else None)
+    step = N.GruStep(o.data_ptr(), d.data_ptr(), h.data_ptr(), out["hx_out"].data_ptr(),
+                     out["actions"].data_ptr(), out["log_probs"].data_ptr(),
+                     out["values"].data_ptr(), out["logits"].data_ptr() if logits else None)
+    N.check(agent.gru.lib.dppo_gru_act_f32(
+        agent.gru.h, agent.flat.flat.data_ptr(), ctypes.byref(step), n, seed, counter,
+        torch.cuda.current_stream().cuda_stream), "dppo_gru_act_f32")
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+
+
+# ---- 1. one step against the float64 module
+@pytest.mark.parametrize("G", WIDTHS)
+@pytest.mark.parametrize("D,A", [(1, 1), (8, 4), (31, 15), (32, 16)])
+@pytest.mark.parametrize("n", [1, ENVS_PER_WG - 1, ENVS_PER_WG + 1, 4101])
+def test_one_step_matches_float64_module(G, n, D, A):
+    agent = _agent(G, D, A)
+    plan = (ctypes.c_int32 * 4)()
+    N.check(agent.gru.lib.dppo_gru_plan(ctypes.byref(agent.gru.dims), plan), "dppo_gru_plan")
+    assert plan[3] == ENVS_PER_WG
+    net = _oracle_net(agent)
+    obs, mixed, hx = _inputs(n, D, G, seed=n * 10 + A)
+    nobs = np.random.default_rng(n).standard_normal((n, D)).astype(np.float32)
+    close = lambda got, want, what: np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL,
+                                                               err_msg=what)
+    for tag, dones in (("mixed", mixed), ("all", np.ones(n, bool)), ("none", np.zeros(n, bool))):
+        got = run_act(agent, obs, dones, hx, seed=5, counter=3)
+        lg, v, h = oracle_step(net, obs, dones, hx)
+        assert h.shape == (n, G)
+        close(got["logits"], lg, tag + " logits")
+        close(got["values"], v, tag + " values")
+        close(got["hx_out"], h, tag + " hx_out")
+        act = got["actions"]
+        assert act.dtype == np.int32 and act.min() >= 0 and act.max() < A
+        close(got["log_probs"], log_softmax64(lg)[np.arange(n), act], tag + " log_probs")
+        if A == 1:
+            assert np.all(act == 0) and np.abs(got["log_probs"]).max() <= 1e-6
+        # V(next_obs) from the step's new hidden state, without and with a reset
+        close(run_value(agent, nobs, got["hx_out"]), oracle_value(net, nobs, got["hx_out"]),
+              tag + " next values")
+        close(run_value(agent, nobs, hx, dones), oracle_value(net, nobs, hx, dones),
+              tag + " values with dones")
+        # the logits are optional
+        lean = run_act(agent, obs, dones, hx, seed=5, counter=3, logits=False)
+        for k in ("hx_out", "actions", "log_probs", "values"):
+            assert np.array_equal(lean[k], got[k]), (tag, k)
+
+
+# ---- 2. the draws are the documented Philox stream, whatever G
+@pytest.mark.parametrize("G", WIDTHS)
+def test_draws_are_the_documented_philox_stream(G):
+    """actions = inverse CDF of the ORACLE's softmax at u01(c0) of Philox4x32-10 (key = seed,
+    counter = {i lo, i hi, ctr lo, ctr hi}), compared exactly where u is more than 1e-5 from every
+    CDF boundary.  A sample misses that margin with probability <= 15 x 2e-5 = 3e-4: about one of
+    the 4101 against an allowance of 1 % (41)."""
+    n, D, A = 4101, 8, 16
+    agent = _agent(G, D, A)
+    net = _oracle_net(agent)
+    obs, dones, hx = _inputs(n, D, G, seed=11)
+    seed, counter = 0x1234_5678_9ABC_DEF1, 77
+    got = run_act(agent, obs, dones, hx, seed, counter)
+    lg, _, _ = oracle_step(net, obs, dones, hx)
+    p = np.exp(log_softmax64(lg))
+    cdf = np.cumsum(p / p.sum(1, keepdims=True), axis=1)
+    i = np.arange(n, dtype=np.uint64)
+    c = philox4x32_10((i & M32, i >> np.uint64(32), np.full(n, counter), np.zeros(n)),
+                      (seed & 0xFFFFFFFF, seed >> 32))
+    u = u01(c[0])
+    want = np.minimum((u[:, None] >= cdf).sum(1), A - 1)
+    clear = np.abs(u[:, None] - cdf[:, :-1]).min(1) > 1e-5
+    assert clear.mean() >= 0.99
+    assert np.array_equal(got["actions"][clear], want[clear])
+    assert len(np.unique(got["actions"])) > A // 2          # the draws use the action range
+    again = run_act(agent, obs, dones, hx, seed, counter)
+    for k in got:
+        assert np.array_equal(got[k], again[k]), k
+    nxt = run_act(agent, obs, dones, hx, seed, counter + 1)
+    assert not np.array_equal(got["actions"], nxt["actions"])
+    for k in ("hx_out", "values", "logits"):                # only the draw depends on the counter
+        assert np.array_equal(got[k], nxt[k]), k
+
+
+# ---- 3. batch independence
+@pytest.mark.parametrize("G", WIDTHS)
+def test_outputs_do_not_depend_on_batch_size_or_position(G):
+    n, D, A = 4101, 8, 4
+    agent = _agent(G, D, A)
+    obs, dones, hx = _inputs(n, D, G, seed=21)
+    big = run_act(agent, obs, dones, hx, seed=2, counter=5)
+    small = run_act(agent, obs[:3], dones[:3], hx[:3], seed=2, counter=5)
+    for k in big:   # same sample indices: the draw and its log-prob agree too
+        assert np.array_equal(big[k][:3], small[k]), k
+    obs2, dones2, hx2 = obs.copy(), dones.copy(), hx.copy()
+    obs2[4098:], dones2[4098:], hx2[4098:] = obs[:3], dones[:3], hx[:3]   # other slots of a workgroup
+    moved = run_act(agent, obs2, dones2, hx2, seed=2, counter=5)
+    for k in ("hx_out", "values", "logits"):
+        assert np.array_equal(moved[k][4098:], small[k]), k
+    v_big = run_value(agent, obs, hx, dones)
+    assert np.array_equal(v_big[:3], run_value(agent, obs[:3], hx[:3], dones[:3]))
+    assert np.array_equal(run_value(agent, obs2, hx2, dones2)[4098:], v_big[:3])
+
+
+# ---- 4. the rollout on it
+def _rollout_agent(G, T, Nn, D, A, fused, **kw):
+    import gym_stub
+    agent = _agent(G, D, A, T=T, Nn=Nn, cache=False, **kw)
+    # episodes end often enough for several hidden resets inside T steps
+    agent.envs = gym_stub.SyncVectorEnv(
+        [lambda: gym_stub.SyntheticEnv(D, A, p_term=0.1, p_trunc=0.05)] * Nn)
+    agent.fused_rollout = fused
+    _start(agent)
+    return agent
+
+
+@pytest.mark.parametrize("G", WIDTHS)
+def test_chained_rollout_matches_the_recomputed_sequence_and_feeds_learn(G):
+    """The fused rollout's cached log_probs / values (chained through T steps in fp32) against
+    GT.sequence in float64 on the rollout's own (obs, prev_dones, hx[0], actions), beside the
+    torch path's fp32 GPU outputs for the same inputs: the fused path may be no further from the
+    float64 result than 4x the torch path's own distance (floor 2e-5), the rule of
+    test_cached_rollout_outputs_match_the_recomputed_sequence.  The rows then feed both learn()
+    paths unchanged."""
+    T, Nn, D, A = 12, 20, 7, 3
+    agent = _rollout_agent(G, T, Nn, D, A, True, num_epochs=2)
+    exp = agent.rollout()
+    torch.cuda.synchronize()
+    assert len(exp) == T and tuple(exp[0][9].shape) == (1, Nn, G)
+    assert tuple(agent.current_hx.shape) == (1, Nn, G)
+    assert torch.all(exp[0][9] == 0) and any(bool(r[5].any()) for r in exp[1:])
+    obs = torch.stack([r[0] for r in exp])
+    act = torch.stack([r[1] for r in exp])
+    pd = torch.stack([r[5] for r in exp])
+    lp_f = torch.stack([r[6] for r in exp]).cpu().double().numpy()
+    v_f = torch.stack([r[7] for r in exp]).cpu().double().numpy()
+    hx0 = exp[0][9]
+    params = {k: torch.from_numpy(p.detach().cpu().double().numpy())
+              for k, p in agent.network.named_parameters()}
+    assert list(params) == GT.GRU_NAMES
+    with torch.no_grad():
+        lg64, v64 = GT.sequence(params, obs.cpu().double(), pd.cpu(), hx0[0].cpu().double())
+        lp64 = torch.log_softmax(lg64, -1).gather(-1, act.cpu()[..., None])[..., 0].numpy()
+        v64 = v64.numpy()
+        lg32, v32, _ = agent.network.get_logits_values_and_hx(obs, hx0, pd)
+        lp32 = torch.distributions.Categorical(logits=lg32).log_prob(act).cpu().double().numpy()
+        v32 = v32.cpu().double().numpy()
+    d_fused = max(np.abs(lp_f - lp64).max(), np.abs(v_f - v64).max())
+    d_torch = max(np.abs(lp32 - lp64).max(), np.abs(v32 - v64).max())
+    print(f"G={G}: d_fused = {d_fused:.3e}  d_torch = {d_torch:.3e}")
+    assert d_fused <= max(4 * d_torch, 2e-5), (d_fused, d_torch)
+    # every row's hx is the previous row's step output: the kernel run again on that row
+    for t in (0, T - 1):
+        row = exp[t]
+        again = run_act(agent, row[0].cpu().numpy(), row[5].cpu().numpy(),
+                        row[9][0].cpu().numpy(), agent._act_seed, t)
+        nxt = exp[t + 1][9] if t + 1 < T else agent.current_hx
+        assert np.array_equal(again["hx_out"], nxt[0].cpu().numpy()), t
+        assert np.array_equal(again["actions"], row[1].cpu().numpy()), t
+        assert np.array_equal(again["log_probs"], row[6].cpu().numpy()), t
+    for fused_gru in (True, False):
+        agent.fused_gru = fused_gru
+        p0 = agent.flat.flat.clone()
+        np.random.seed(3)
+        agent.learn(exp)
+        torch.cuda.synchronize()
+        assert torch.isfinite(agent.flat.flat).all()
+        assert float((agent.flat.flat - p0).abs().max()) > 1e-5, fused_gru
+
+
+@pytest.mark.parametrize("G", WIDTHS)
+def test_default_rollout_still_draws_from_torch(G):
+    """fused_rollout = False (the default): the actions under torch.manual_seed(s) are those of
+    the torch ops rollout() has always run, restated here inline."""
+    T, Nn, D, A, s = 6, 8, 4, 2, 1234
+    agent = _rollout_agent(G, T, Nn, D, A, False)
+    torch.manual_seed(s)
+    exp = agent.rollout()
+    ref = _rollout_agent(G, T, Nn, D, A, False)
+    torch.manual_seed(s)
+    obs, hx, pd = ref.current_observations, ref.current_hx, ref.prev_dones
+    for t in range(T):
+        obs_t = torch.as_tensor(obs[None, ...], dtype=torch.float32, device=ref.device)
+        pd_t = torch.as_tensor(pd[None, ...], dtype=torch.bool, device=ref.device)
+        with torch.inference_mode():
+            logits, values, new_hx = ref.network.get_logits_values_and_hx(obs_t, hx, pd_t)
+        dist = torch.distributions.Categorical(logits=logits.squeeze(0))
+        actions = dist.sample()
+        log_probs = dist.log_prob(actions)
+        nobs, rew, term, trunc, _ = ref.envs.step(actions.cpu().numpy())
+        assert torch.equal(exp[t][1], actions), t
+        assert exp[t][1].dtype == torch.int64
+        assert torch.equal(exp[t][6], log_probs) and torch.equal(exp[t][7], values.squeeze(0))
+        assert torch.equal(exp[t][9], hx) and np.array_equal(exp[t][2], rew)
+        dones = np.logical_or(term, trunc)
+        obs = ref.envs.reset(options={"reset_mask": dones})[0] if np.any(dones) else nobs
+        hx, pd = new_hx, dones

@@ -9,6 +9,11 @@ same weights, `fused_rollout` on and off, run their rollouts alternately (whatev
 host hits both alike): `--warmup` untimed rollouts each, then `--rollouts` timed ones, every one
 bracketed by a device synchronisation and the host wall clock (a rollout is 2-100 ms).  Reported:
 the median ms per rollout() of each path with min / max, and torch / fused.
+`--gru-hidden G [G ...]` (default 16) runs other GRU widths, one after the other; 32 and 64 use
+the kernels of csrc/gruactwide.hip, and a result row of a width other than 16 carries "G":
+
+    python tools/bench_recurrent_rollout.py --gru-hidden 32 64 \
+        --out profiles/recurrent_wide_rollout.json
 
 In a separate pass (events on every launch slow the host) the library's timing mode
 (dppo_gru_set_timing) gives the two kernels' own execution time per launch.
@@ -35,11 +40,12 @@ T, D, A = 32, 8, 4
 SIZES = [32, 1024, 8192]
 
 
-def make_agent(Nn, fused):
+def make_agent(Nn, fused, G=16):
     np.random.seed(0)
     torch.manual_seed(0)
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
-    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False)
+    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
+                                     gru_hidden_dim=G)
     agent = diamond.RecurrentPPO(None, cfg, envs=envs)
     assert agent.gru is not None
     agent.fused_rollout = fused
@@ -57,8 +63,8 @@ def timed_rollout(agent):
     return (time.perf_counter() - t0) * 1e3
 
 
-def run(Nn, warmup, rollouts, kernel_rollouts):
-    agents = {"fused": make_agent(Nn, True), "torch": make_agent(Nn, False)}
+def run(Nn, warmup, rollouts, kernel_rollouts, G=16):
+    agents = {"fused": make_agent(Nn, True, G), "torch": make_agent(Nn, False, G)}
     ms = {k: [] for k in agents}
     for r in range(warmup + rollouts):
         for k, agent in agents.items():
@@ -66,6 +72,8 @@ def run(Nn, warmup, rollouts, kernel_rollouts):
             if r >= warmup:
                 ms[k].append(t)
     out = {"N": Nn, "T": T, "D": D, "A": A, "warmup": warmup, "rollouts": rollouts}
+    if G != 16:
+        out = {"G": G, **out}
     for k, v in ms.items():
         out[k + "_ms_median"] = statistics.median(v)
         out[k + "_ms_min"], out[k + "_ms_max"] = min(v), max(v)
@@ -89,12 +97,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rollouts", type=int, default=20)
     ap.add_argument("--kernel-rollouts", type=int, default=5)
+    ap.add_argument("--gru-hidden", type=int, nargs="+", default=[16])
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "sizes": []}
-    for Nn in SIZES:
-        r = run(Nn, a.warmup, a.rollouts, a.kernel_rollouts)
-        print(json.dumps(r), flush=True)
-        res["sizes"].append(r)
+    for G in a.gru_hidden:
+        for Nn in SIZES:
+            r = run(Nn, a.warmup, a.rollouts, a.kernel_rollouts, G)
+            print(json.dumps(r), flush=True)
+            res["sizes"].append(r)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
