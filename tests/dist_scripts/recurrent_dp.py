@@ -32,7 +32,7 @@ def shard(exp, lo, hi):
     return out
 
 
-def run(rank, world, port, T, Ng, D, A, out_path):
+def run(rank, world, port, T, Ng, D, A, out_path, gru_hidden_dim=16):
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     for p in (os.path.join(root, "diamond-ppo_amd"), os.path.join(root, "tests", "golden")):
         if p not in sys.path:
@@ -48,9 +48,11 @@ def run(rank, world, port, T, Ng, D, A, out_path):
     import gym_stub
     Nl = Ng // world
     cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nl, num_epochs=3,
-                                     num_minibatches=1, verbose=False)
+                                     num_minibatches=1, verbose=False,
+                                     gru_hidden_dim=gru_hidden_dim)
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nl)
     agent = diamond.RecurrentPPO(None, cfg, envs=envs)
+    assert agent.gru is not None, "gru_hidden_dim %d did not take the fused path" % gru_hidden_dim
     exp = synth_experience(T, Ng, D, A, cfg.gru_hidden_dim, agent.device)
     init = agent.flat.flat.cpu().numpy()
     agent.learn(shard(exp, rank * Nl, (rank + 1) * Nl))

@@ -60,21 +60,22 @@ CASES = (
 )
 
 
-def initial_params(D, A, seed=42):
-    """RecurrentPPO's initial weights for RecurrentPPOConfig(seed=seed), built on the CPU."""
+def initial_params(D, A, seed=42, G=G):
+    """RecurrentPPO's initial weights for RecurrentPPOConfig(gru_hidden_dim=G, seed=seed), built
+    on the CPU."""
     import gym_stub
     from diamond.recurrent_ppo import (RecurrentActorCriticNetwork, RecurrentPPOConfig,
                                        network_parameter_init_)
     torch.manual_seed(seed)
     net = RecurrentActorCriticNetwork(gym_stub.Box(shape=(D,)), gym_stub.Discrete(A),
-                                      cfg=RecurrentPPOConfig())
+                                      cfg=RecurrentPPOConfig(gru_hidden_dim=G))
     network_parameter_init_(net, gain=sqrt(2.0))
     p = {n: t.detach().numpy().copy() for n, t in net.named_parameters()}
     assert list(p) == GT.GRU_NAMES
     return p
 
 
-def data(T, Nn, D, A, seed):
+def data(T, Nn, D, A, seed, G=G):
     rng = np.random.default_rng(seed)
     return dict(obs=rng.standard_normal((T, Nn, D)).astype(np.float32),
                 actions=rng.integers(0, A, (T, Nn)).astype(np.int32),
@@ -96,13 +97,15 @@ def scaled_params(params, case):
 
 
 def build(case):
-    """(params, data dict, mb_idx int32, m_total) of one case."""
+    """(params, data dict, mb_idx int32, m_total) of one case, at the case's own G where it has
+    one (tests/gru_wide_cases.py) and at 16 otherwise."""
     T, Nn, D, A = case.shape
+    width = getattr(case, "G", G)
     seed = T * 100 + Nn + case.seed_shift
     rng = np.random.default_rng(seed + 1)
     params = {n: (p + 0.3 * rng.standard_normal(p.shape)).astype(np.float32)
-              for n, p in initial_params(D, A).items()}
-    x = data(T, Nn, D, A, seed)
+              for n, p in initial_params(D, A, G=width).items()}
+    x = data(T, Nn, D, A, seed, G=width)
     params = scaled_params(params, case)
     if case.obs_scale != 1.0:
         x["obs"] = x["obs"] * np.float32(case.obs_scale)

@@ -8,14 +8,9 @@ A case's ``seed_shift`` moves the seed of its weights and data; it is 0 unless t
 there (a selected sample within 1e-4 of a clip edge, or fewer than 20 % of the samples on one side
 of the clip), and tests/test_gru_wide_cpu.py is the proof that the chosen ones hold."""
 from dataclasses import dataclass, replace
-from math import sqrt
-
-import numpy as np
-import torch
 
 import gru_cases
 from gru_cases import KTAIL_SHAPES, MID, guards  # noqa: F401  (re-exported)
-from oracle import gru_torch as GT
 
 WIDTHS = (32, 64)
 # envs per workgroup of the gradient kernel (256 threads, G lanes per env); dppo_gru_plan reports
@@ -56,6 +51,49 @@ SEED_SHIFT = {(64, "ktail-5x3x4x2-1.0"): 1}   # at 0: 2 of its 15 samples clippe
 CASES = [replace(c, seed_shift=SEED_SHIFT.get((c.G, c.name), 0)) for G in WIDTHS for c in _cases(G)]
 
 
+# Sequences of more than one pass and many slabs.  A workgroup holds S = T * ne samples of its
+# ne <= ENVS_PER_WG envs and walks them 256 at a time; the gradient slabs are one per workgroup.
+# Per G: a full workgroup just past one pass; a full and a partial workgroup past one pass; the
+# same at D = 32, A = 16 with a 1-env tail; three passes; the class default (S = 256 exactly at
+# G = 32, no thread idle and no second pass); and 1030 envs (129 / 258 slabs, a partial last
+# workgroup).  Each runs off-policy at frac 1.0 and 0.4 and on-policy at 1.0; the (40, 15) /
+# (72, 7) shape also with the dones patterns that reset the BPTT carry at every step of one env
+# and at the last step of all.
+LONG_SHAPES = {
+    32: [(33, 8, 5, 3), (40, 15, 5, 3), (40, 17, 32, 16), (70, 9, 4, 2), (32, 32, 4, 2),
+         (2, 1030, 5, 3)],
+    # (90, 7): at 4 envs per workgroup a partial one needs T >= 86 to pass 256 samples
+    64: [(65, 4, 5, 3), (72, 7, 5, 3), (90, 7, 5, 3), (72, 9, 32, 16), (130, 5, 4, 2),
+         (32, 32, 4, 2), (2, 1030, 5, 3)],
+}
+LONG_DONES_SHAPE = {32: (40, 15, 5, 3), 64: (72, 7, 5, 3)}
+MANY_ENVS = (2, 1030, 5, 3)     # compared with its first 1024 envs alone (test_gpu_gru_wide.py)
+MANY_ENVS_HEAD = 1024
+
+
+def _long_cases(G):
+    x = lambda s: "x".join(map(str, s))
+    return (
+        [Case(f"long-{x(s)}-{f}", s, frac=f, G=G) for s in LONG_SHAPES[G] for f in (1.0, 0.4)]
+        + [Case(f"long-onpolicy-{x(s)}", s, on_policy=True, G=G) for s in LONG_SHAPES[G]]
+        + [Case(f"long-dones-{d}-{x(LONG_DONES_SHAPE[G])}", LONG_DONES_SHAPE[G], dones=d, G=G)
+           for d in ("env_always", "last")])
+
+
+# at 0: a ratio 7e-5 / 3e-5 from a clip edge
+SEED_SHIFT.update({(32, "long-70x9x4x2-1.0"): 1, (64, "long-90x7x5x3-1.0"): 1})
+
+LONG_CASES = [replace(c, seed_shift=SEED_SHIFT.get((c.G, c.name), 0))
+              for G in WIDTHS for c in _long_cases(G)]
+
+
+def workgroups(case):
+    """[(envs, samples S)] of the gradient kernel's workgroups on one case."""
+    T, Nn = case.shape[:2]
+    E = ENVS_PER_WG[case.G]
+    return [(min(E, Nn - lo), T * min(E, Nn - lo)) for lo in range(0, Nn, E)]
+
+
 def config(G, **kw):
     from diamond.recurrent_ppo import RecurrentPPOConfig
     return RecurrentPPOConfig(gru_hidden_dim=G, **kw)
@@ -64,55 +102,15 @@ def config(G, **kw):
 def initial_params(D, A, G, seed=42):
     """RecurrentPPO's initial weights for RecurrentPPOConfig(gru_hidden_dim=G, seed=seed), built
     on the CPU."""
-    import gym_stub
-    from diamond.recurrent_ppo import RecurrentActorCriticNetwork, network_parameter_init_
-    torch.manual_seed(seed)
-    net = RecurrentActorCriticNetwork(gym_stub.Box(shape=(D,)), gym_stub.Discrete(A),
-                                      cfg=config(G))
-    network_parameter_init_(net, gain=sqrt(2.0))
-    p = {n: t.detach().numpy().copy() for n, t in net.named_parameters()}
-    assert list(p) == GT.GRU_NAMES
-    return p
+    return gru_cases.initial_params(D, A, seed, G=G)
 
 
 def data(T, Nn, D, A, G, seed):
-    rng = np.random.default_rng(seed)
-    return dict(obs=rng.standard_normal((T, Nn, D)).astype(np.float32),
-                actions=rng.integers(0, A, (T, Nn)).astype(np.int32),
-                old_log_probs=(-rng.uniform(0.2, 1.5, (T, Nn))).astype(np.float32),
-                advantages=rng.standard_normal((T, Nn)).astype(np.float32),
-                returns=rng.standard_normal((T, Nn)).astype(np.float32),
-                prev_dones=(rng.random((T, Nn)) < 0.08),
-                hx0=(rng.standard_normal((Nn, G)) * 0.5).astype(np.float32))
+    return gru_cases.data(T, Nn, D, A, seed, G=G)
 
 
 def build(case):
-    """(params, data dict, mb_idx int32, m_total) of one case: gru_cases.build at case.G."""
-    T, Nn, D, A = case.shape
-    seed = T * 100 + Nn + case.seed_shift
-    rng = np.random.default_rng(seed + 1)
-    params = {n: (p + 0.3 * rng.standard_normal(p.shape)).astype(np.float32)
-              for n, p in initial_params(D, A, case.G).items()}
-    x = data(T, Nn, D, A, case.G, seed)
-    pd = x["prev_dones"]
-    if case.dones == "none":
-        pd[:] = False
-    elif case.dones == "first":
-        pd[0] = True
-    elif case.dones == "env_always":
-        pd[:, gru_cases.DONE_ENV] = True
-    elif case.dones == "last":
-        pd[:] = False
-        pd[T - 1] = True
-    else:
-        assert case.dones == "random"
-    if case.on_policy:
-        lp = GT.log_probs(params, x["obs"], x["actions"], pd, x["hx0"])
-        x["old_log_probs"] = lp.astype(np.float32)
-    B = T * Nn
-    if case.pick is not None:
-        mb_idx = np.array([case.pick[0] * Nn + case.pick[1]], np.int32)
-    else:
-        m = max(1, int(B * case.frac))
-        mb_idx = np.random.default_rng(7).permutation(B)[:m].astype(np.int32)
-    return params, x, mb_idx, case.m_total_mul * len(mb_idx)
+    """(params, data dict, mb_idx int32, m_total) of one case: gru_cases.build at case.G, regime
+    fields (tests/regime_cases.py) included."""
+    assert case.G in WIDTHS
+    return gru_cases.build(case)

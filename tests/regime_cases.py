@@ -15,6 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 
 import gru_cases
+import gru_wide_cases
 from diamond import _native as N
 from oracle import gru_torch as GT
 from oracle import ppo_np as P
@@ -275,8 +276,70 @@ GRU_CASES = [gru_cases.Case(f"{r}-{'x'.join(map(str, s))}-{'on' if on else 'off'
              for r, row in GRU_REGIMES.items() for s, kw in row.items() for on in (True, False)]
 
 
+# ---------------------------------------------------------------------------------------------
+# The same five regimes at gru_hidden_dim 32 and 64 (csrc/gruwide.hip, csrc/gruactwide.hip), through
+# gru_wide_cases.Case.  The G = 16 scales do not carry over: the heads read 32 / 64 hidden units, so
+# the same actor_scale gives gaps of 65 to 157, and the recurrent map at gru_scale 5 - 6 is chaotic
+# at these widths (the float32 autograd oracle itself ends 7e-5 .. 2e-2 of max|g| from the float64
+# one).  The scales were chosen per (G, shape) with the oracles alone, never with a kernel:
+#   peaked20 / peaked30: the smallest actor_scale on a 0.5 grid that reaches the regime;
+#   hidden6: the largest gru_scale of 6, 5, 4, 3.5, 3, 2.5, 2 that reaches it;
+#   seed_shift: the first of base .. base + 7, base 0, 1000, 2000, 3000, at which the guards hold
+#   and the float32 oracle is under 0.85 of the cap (room for another BLAS) both on- and off-policy.
+# Reached (float64) and err_oracle32 (on / off):
+#   G 32 (7,17,5,3)    peaked20 gap 56.5   2.7e-6 / 3.1e-6    peaked30 gap 103.7 logp -83.1  3.2e-6 / 3.5e-6
+#   G 32 (9,18,32,16)  peaked20 gap 56.0   1.5e-6 / 2.3e-6    peaked30 gap  90.8 logp -90.8  5.3e-6 / 6.1e-6
+#   G 64 (7,17,5,3)    peaked20 gap 57.3   4.5e-6 / 6.7e-6    peaked30 gap  90.7 logp -90.7  5.6e-6 / 8.0e-6
+#   G 64 (9,18,32,16)  peaked20 gap 56.9   2.3e-6 / 3.1e-6    peaked30 gap  98.0 logp -84.7  7.0e-6 / 7.6e-6
+#   obs30: 0.84 - 0.95 of the base units saturated, 7.3e-7 .. 7.0e-6; returns100: 3.3e-7 .. 7.1e-7
+# Far rows (GRU_WIDE_FAR): hidden6, all four.  At every grid scale that reaches the regime (>= 3.5)
+# the recurrent map amplifies rounding from step to step, so the float32 oracle's error is a
+# draw from a wide band rather than a property of the case: over seeds 0 .. 7 it spans 1e-5 .. 9e-3
+# at G 64 and 4e-6 .. 3e-4 at G 32, a run under NEAR_CAP on one machine is at 2e-5 on another CPU,
+# and one ulp on the weights (gru_oracle32_nudged) moves it by a factor of up to 50.  No scale has
+# a seed among the 32 at which the float32 oracle and its three nudged draws all meet NEAR_CAP, on-
+# and off-policy; so these rows run on-policy only, at gru_scale 6, the largest grid scale at which
+# a seed has the float32 oracle and its nudged draws under 0.85 FAR_CAP (the first such seed):
+#   G 32 (7,17,5,3)    gates 0.55 candidates 0.69   err_oracle32 1.9e-4, nudged to 3.2e-4
+#   G 32 (9,18,32,16)  gates 0.65 candidates 0.79   1.6e-4, nudged to 4.0e-4
+#   G 64 (7,17,5,3)    gates 0.60 candidates 0.69   1.4e-4, nudged to 2.2e-4   (seed_shift 3)
+#   G 64 (9,18,32,16)  gates 0.66 candidates 0.78   1.6e-4, nudged to 5.9e-4   (seed_shift 6)
+# The kernel is held to the far rule there: finite, err <= 4 err_oracle32 + 1e-6, err <= 1e-3.
+# ---------------------------------------------------------------------------------------------
+GRU_WIDE_REGIMES = {   # (G, shape) -> {name: Case fields}
+    (32, _MID): {"obs30": dict(obs_scale=30.0), "hidden6": dict(gru_scale=6.0),
+                 "peaked20": dict(actor_scale=6.0), "peaked30": dict(actor_scale=11.0),
+                 "returns100": dict(ret_scale=100.0)},
+    (32, _BIG): {"obs30": dict(obs_scale=30.0), "hidden6": dict(gru_scale=6.0),
+                 "peaked20": dict(actor_scale=6.5), "peaked30": dict(actor_scale=10.5),
+                 "returns100": dict(ret_scale=100.0)},
+    (64, _MID): {"obs30": dict(obs_scale=30.0), "hidden6": dict(gru_scale=6.0, seed_shift=3),
+                 "peaked20": dict(actor_scale=6.0), "peaked30": dict(actor_scale=9.5),
+                 "returns100": dict(ret_scale=100.0)},
+    (64, _BIG): {"obs30": dict(obs_scale=30.0), "hidden6": dict(gru_scale=6.0, seed_shift=6),
+                 "peaked20": dict(actor_scale=4.5),
+                 "peaked30": dict(actor_scale=9.0, seed_shift=1001),
+                 "returns100": dict(ret_scale=100.0)},
+}
+GRU_WIDE_FAR = {("hidden6", g, s) for g in gru_wide_cases.WIDTHS for s in GRU_SHAPES}
+GRU_WIDE_CASES = [gru_wide_cases.Case(f"{r}-{'x'.join(map(str, s))}-{'on' if on else 'off'}", s,
+                                      frac=1.0 if on else 0.4, on_policy=on,
+                                      old_noise=0.0 if on else GRU_OLD_NOISE, G=g, **kw)
+                  for (g, s), row in GRU_WIDE_REGIMES.items() for r, kw in row.items()
+                  for on in (True, False) if on or (r, g, s) not in GRU_WIDE_FAR]
+
+
+def gru_build(case):
+    """gru_cases.build, or gru_wide_cases.build for a case with a G of its own."""
+    return (gru_wide_cases.build if hasattr(case, "G") else gru_cases.build)(case)
+
+
 def gru_regime(case):
     return case.name.split("-")[0]
+
+
+def gru_is_far(case):
+    return (gru_regime(case), getattr(case, "G", gru_cases.G), case.shape) in GRU_WIDE_FAR
 
 
 def gru_reached(params, x):
@@ -286,7 +349,7 @@ def gru_reached(params, x):
     d = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
     p = {k: d(v) for k, v in params.items()}
     obs, pd, h = d(x["obs"]), torch.as_tensor(np.asarray(x["prev_dones"], bool)), d(x["hx0"])
-    G = gru_cases.G
+    G = p["gru.weight_hh_l0"].shape[1]
     F = torch.nn.functional
     x1 = torch.tanh(F.linear(obs, p["base.0.weight"], p["base.0.bias"]))
     gi = F.linear(x1, p["gru.weight_ih_l0"], p["gru.bias_ih_l0"])
@@ -324,6 +387,28 @@ def gru_oracle_pair(case, params, x, mb_idx, m_total):
     return res, float(err)
 
 
+def gru_oracle32_nudged(case, params, x, mb_idx, m_total, draws=3):
+    """err_oracle32 of the float32 oracle run on weights moved by one float32 ulp each, up or
+    down at random (seeded), against the float64 oracle on the weights as they are: what another
+    rounding of the same arithmetic does to the figure.  Where the recurrent map is chaotic (large
+    gru_scale at gru_hidden_dim 32 / 64) it moves by a factor of up to 50, and one float32 run under
+    a cap says little; the wide hidden6 rows are chosen so that these draws meet the cap as well."""
+    import torch
+    a = (x["obs"], x["actions"], x["old_log_probs"], x["advantages"], x["returns"],
+         x["prev_dones"], x["hx0"], mb_idx, m_total, case.clip, case.vf, case.ent)
+    g64 = GT.minibatch_grads(params, *a, dt=torch.float64)[1]
+    scale = max(np.abs(g).max() for g in g64.values())
+    rng = np.random.default_rng(1)
+    errs = []
+    for _ in range(draws):
+        p = {n: np.nextafter(v, np.where(rng.random(v.shape) < 0.5, -np.inf, np.inf).astype(f32))
+             for n, v in params.items()}
+        g32 = GT.minibatch_grads(p, *a, dt=torch.float32)[1]
+        errs.append(float(max(np.abs(g32[n].astype(np.float64) - g64[n]).max() for n in g64)
+                          / scale))
+    return errs
+
+
 # ---------------------------------------------------------------------------------------------
 # Rollout samplers: n = 33 observations per (regime, shape).
 # ---------------------------------------------------------------------------------------------
@@ -352,21 +437,24 @@ def sampler_inputs(regime, shape):
     return params, flat32(L, names, params), obs
 
 
-def gru_sampler_inputs(regime, D, A):
-    """(params, obs [n][D], prev dones [n], hidden state [n][16], next obs) of one GRU rollout-step
-    case: tests/gru_cases.py's weights in the regime, the inputs of tests/test_gpu_gru_act.py."""
-    kw = next(dict(kw) for s, kw in GRU_REGIMES[regime].items() if s[2:] == (D, A))
+def gru_sampler_inputs(regime, D, A, G=gru_cases.G):
+    """(params, obs [n][D], prev dones [n], hidden state [n][G], next obs) of one GRU rollout-step
+    case: tests/gru_cases.py's weights in the regime (at G = 32 / 64 with the scales of
+    GRU_WIDE_REGIMES), the inputs of tests/test_gpu_gru_act.py."""
+    table = GRU_REGIMES[regime] if G == gru_cases.G else \
+        {s: row[regime] for (g, s), row in GRU_WIDE_REGIMES.items() if g == G}
+    kw = next(dict(kw) for s, kw in table.items() if s[2:] == (D, A))
     kw.pop("seed_shift", None)
     case = gru_cases.Case(regime, (1, SAMPLER_N, D, A), **kw)
     rng = np.random.default_rng(600 + D)
     params = {n: (p + 0.3 * rng.standard_normal(p.shape)).astype(f32)
-              for n, p in gru_cases.initial_params(D, A).items()}
+              for n, p in gru_cases.initial_params(D, A, G=G).items()}
     params = gru_cases.scaled_params(params, case)
     k = f32(case.obs_scale)
     obs = rng.standard_normal((SAMPLER_N, D)).astype(f32) * k
     nobs = rng.standard_normal((SAMPLER_N, D)).astype(f32) * k
     dones = rng.random(SAMPLER_N) < 0.3
-    hx = (rng.standard_normal((SAMPLER_N, gru_cases.G)) * 0.5).astype(f32)
+    hx = (rng.standard_normal((SAMPLER_N, G)) * 0.5).astype(f32)
     return params, obs, dones, hx, nobs
 
 

@@ -11,7 +11,8 @@ the reference's arithmetic.  tests/test_regimes_cpu.py shows with the oracle alo
 regime is reached and that the reference's own float32 arithmetic meets the bounds used here.
 
 a. the minibatch gradient of all four families (dppo_prepare_f32 + dppo_minibatch_grad_f32 as
-   tests/test_gpu_shapes.py runs them; dppo_gru_minibatch_grad_f32 as tests/test_gpu_gru.py)
+   tests/test_gpu_shapes.py runs them; dppo_gru_minibatch_grad_f32 as tests/test_gpu_gru.py, at
+   gru_hidden_dim 16 and, with the scales of regime_cases.GRU_WIDE_REGIMES, at 32 and 64)
    against the float64 oracle: on-policy in every regime, off-policy (gpu_helpers.offpolicy_inputs
    with the regime's transform) in the near ones.  Near regimes: the bounds of
    tests/test_gpu_production.py -- err_kernel <= 2e-5, err_kernel <= 4 err_oracle32 + 1e-6, each
@@ -19,15 +20,16 @@ a. the minibatch gradient of all four families (dppo_prepare_f32 + dppo_minibatc
    Far regimes (float32 itself degrades): everything finite, err_kernel <= 4 err_oracle32 + 1e-6,
    loss terms within 4 |loss32 - loss64| + 2e-5 max(1, |x|); err_oracle32 is the float32 oracle's
    own distance from the float64 one on the same records.  One (family, regime) misses that and
-   has the bound of FAR_MEASURED instead.
+   has the bound of FAR_MEASURED instead.  The wide GRU's hidden6 rows are far (the recurrent map
+   is chaotic there: regime_cases.GRU_WIDE_FAR) and keep the rule as it stands.
 b. the old-policy evaluation behind dppo_prepare_f32 (eval_kernel, the wide eval): log-probs,
    values and next values within 2e-5 max(1, |exact|) + 4 |oracle32 - exact| of the float64 oracle
    per element (combined: a max-norm bound, see EVAL_MAX_NORM); returns == values + gae(values)
    bit for bit.
-c. the rollout samplers (act_kernel, wide_act_kernel, the GRU act and next-value kernels) at
-   n = 33: heads / log-probs / values with the bound of b, discrete draws equal to the inverse CDF
-   of the float64 softmax on every sample (all are clear of the CDF boundaries), Gaussian draws
-   and the squash as tests/test_gpu_wide_act.py checks them.
+c. the rollout samplers (act_kernel, wide_act_kernel, the GRU act and next-value kernels of all
+   three widths) at n = 33: heads / log-probs / values with the bound of b, discrete draws equal
+   to the inverse CDF of the float64 softmax on every sample (all are clear of the CDF
+   boundaries), Gaussian draws and the squash as tests/test_gpu_wide_act.py checks them.
 d. one whole learn() per MLP family under obs30 and peaked20 (test_gpu_production.learn_vs_oracle
    with the regime's transform).
 
@@ -251,11 +253,15 @@ def test_offpolicy_minibatch_gradient_in_regime(case):
 # ---------------------------------------------------------------------------------------------
 # a. GRU
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.GRU_CASES, ids=str)
+@pytest.mark.parametrize("case", R.GRU_CASES + R.GRU_WIDE_CASES, ids=str)
 def test_gru_minibatch_gradient_in_regime(case):
-    from test_gpu_gru import _case_agent, _kernel_grad
+    from test_gpu_gru import _kernel_grad
     from oracle import gru_torch as GT
-    params, x, mb_idx, m_total = gru_cases.build(case)
+    if hasattr(case, "G"):      # gru_hidden_dim 32 / 64: csrc/gruwide.hip
+        from test_gpu_gru_wide import _case_agent
+    else:
+        from test_gpu_gru import _case_agent
+    params, x, mb_idx, m_total = R.gru_build(case)
     gru_cases.guards(case, params, x, mb_idx)
     agent = _case_agent(case, params)
     L = agent.gru.layout
@@ -270,18 +276,24 @@ def test_gru_minibatch_gradient_in_regime(case):
     err = max(per.values()) / scale
     print(f"REGIME gru {case}: err_kernel {err:.3g} err_oracle32 {err32:.3g}")
     assert np.isfinite(g).all()
-    assert err <= 2e-5, (err, err32)
     assert err <= 4 * err32 + 1e-6, (err, err32)
-    for n in GT.GRU_NAMES:
-        own = max(np.abs(ref[n]).max(), 1e-3 * scale)
-        assert per[n] <= 1e-4 * own, (n, per[n] / own)
+    if R.gru_is_far(case):
+        # float32 itself degrades (regime_cases.GRU_WIDE_FAR): the far rule of _check_gradient
+        assert case.on_policy and err <= 1e-3, (err, err32)
+        s32 = res[torch.float32][0]
+    else:
+        assert err <= 2e-5, (err, err32)
+        for n in GT.GRU_NAMES:
+            own = max(np.abs(ref[n]).max(), 1e-3 * scale)
+            assert per[n] <= 1e-4 * own, (n, per[n] / own)
+        s32 = s64
 
     def terms(s):
         pi, vl, en = (float(v) / m_total for v in s)
         return pi + case.vf * vl - case.ent * en, pi, vl, en
 
-    for got, x64 in zip(terms(g[L.total:L.total + 3]), terms(s64)):
-        assert abs(got - x64) <= 2e-5 * max(1.0, abs(x64)), (got, x64)
+    for got, x64, x32 in zip(terms(g[L.total:L.total + 3]), terms(s64), terms(s32)):
+        assert abs(got - x64) <= 4 * abs(x32 - x64) + 2e-5 * max(1.0, abs(x64)), (got, x64)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -334,7 +346,10 @@ def test_mlp_sampler_in_regime(case):
 
 
 @functools.lru_cache(maxsize=None)
-def _gru_agent(D, A):
+def _gru_agent(D, A, G=gru_cases.G):
+    if G != gru_cases.G:
+        from test_gpu_gru_wide_act import _agent as wide_agent
+        return wide_agent(G, D, A, T=2, Nn=4, spread=False)
     from test_gpu_gru_act import _agent
     return _agent(2, 4, D, A, spread=False)
 
@@ -363,13 +378,16 @@ def _gru_value(net, dt, obs, hx):
         return net.get_values(t(obs)[None], t(hx)[None], None)[0].double().numpy()
 
 
-@pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
-@pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
-def test_gru_sampler_in_regime(regime, D, A):
-    from test_gpu_gru_act import log_softmax64, run_act, run_value
+def _gru_sampler(regime, D, A, G):
+    from test_gpu_gru_act import log_softmax64, run_value
+    if G == gru_cases.G:
+        from test_gpu_gru_act import run_act
+    else:
+        from test_gpu_gru_wide_act import run_act
     n = R.SAMPLER_N
-    params, obs, dones, hx, nobs = R.gru_sampler_inputs(regime, D, A)
-    agent = _gru_agent(D, A)
+    params, obs, dones, hx, nobs = R.gru_sampler_inputs(regime, D, A, G)
+    agent = _gru_agent(D, A, G)
+    assert agent.gru is not None and agent.gru.dims.gru_hidden == G == hx.shape[1]
     with torch.no_grad():
         for name, p in agent.network.named_parameters():
             p.copy_(torch.from_numpy(params[name]))
@@ -390,10 +408,25 @@ def test_gru_sampler_in_regime(regime, D, A):
     nv = _within(run_value(agent, nobs, got["hx_out"]),
                  _gru_value(net64, torch.float64, nobs, got["hx_out"]),
                  _gru_value(net32, torch.float32, nobs, got["hx_out"]), "next values")
-    print(f"REGIME gru sampler {regime}-D{D}-A{A}: max |kernel - f64| / |oracle32 - f64| logits "
+    print(f"REGIME gru sampler {regime}-D{D}-A{A}-G{G}: max |kernel - f64| / |oracle32 - f64| "
+          f"logits "
           f"{figs[0][0]:.3g} / {figs[0][1]:.3g} values {figs[1][0]:.3g} / {figs[1][1]:.3g} hx "
           f"{figs[2][0]:.3g} / {figs[2][1]:.3g} log_probs {lp[0]:.3g} / {lp[1]:.3g} next values "
           f"{nv[0]:.3g} / {nv[1]:.3g}")
+
+
+@pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
+@pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
+def test_gru_sampler_in_regime(regime, D, A):
+    _gru_sampler(regime, D, A, gru_cases.G)
+
+
+@pytest.mark.parametrize("G", R.gru_wide_cases.WIDTHS)
+@pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
+@pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
+def test_gru_wide_sampler_in_regime(regime, D, A, G):
+    """The same at gru_hidden_dim 32 and 64 (csrc/gruactwide.hip), with GRU_WIDE_REGIMES' scales."""
+    _gru_sampler(regime, D, A, G)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,14 +1,16 @@
 """Host-side surface of the fused GRU kernels at gru_hidden_dim 16, 32 and 64 (csrc/gru.hip host
 code, diamond.recurrent_ppo.fused_gru_shape): the flat layout libdppo reports for a G is
 FlatParams' for the network with that G, the Python predicate is the documented set, and the
-clip-regime guards of every wide gradient case (tests/gru_wide_cases.py) hold on the float64 oracle
-alone.  The kernels themselves: tests/test_gpu_gru_wide.py, tests/test_gpu_gru_wide_act.py."""
+clip-regime guards of every wide gradient case (tests/gru_wide_cases.py, the long ones included)
+hold on the float64 oracle alone, and the long cases reach the multi-pass and many-slab code.
+The kernels themselves: tests/test_gpu_gru_wide.py, tests/test_gpu_gru_wide_act.py."""
 import ctypes
 import itertools
 
 import pytest
 import torch
 
+import gru_cases
 import gru_wide_cases as W
 from diamond import _native as N
 from diamond.engine import FlatParams
@@ -102,3 +104,51 @@ def test_wide_gradient_case_guards_hold(case):
     assert m_total == case.m_total_mul * len(mb_idx) and len(set(mb_idx.tolist())) == len(mb_idx)
     edge, share = W.guards(case, params, x, mb_idx)
     print(f"{case}: m={len(mb_idx)} nearest edge {edge:.3e} zero-policy-gradient share {share:.2f}")
+
+
+@pytest.mark.parametrize("case", W.LONG_CASES, ids=str)
+def test_long_gradient_case_guards_hold(case):
+    test_wide_gradient_case_guards_hold(case)
+
+
+def test_long_case_list_reaches_multi_pass_and_many_slabs():
+    """What LONG_CASES is for, derived from ENVS_PER_WG and the kernel's 256 threads: per G a
+    full and a partial workgroup whose S = T * ne samples need a second pass, one that needs a
+    third, more than 100 gradient slabs, and the class default shape (at 8 envs per workgroup S =
+    256 exactly: the last size of one pass) -- and the slab count is the plan's."""
+    names = {str(c) for c in W.LONG_CASES}
+    assert len(names) == len(W.LONG_CASES) and not names & {str(c) for c in W.CASES}
+    known = {s[2:] for s in W.KTAIL_SHAPES}
+    lib = N.load()
+    out = (ctypes.c_int32 * 4)()
+    for G in W.WIDTHS:
+        E = W.ENVS_PER_WG[G]
+        cases = [c for c in W.LONG_CASES if c.G == G]
+        assert all(c.shape[2:] in known for c in cases)
+        full, partial, three, exact, slabs = set(), set(), set(), set(), set()
+        for c in cases:
+            T, Nn, D, A = c.shape
+            wgs = W.workgroups(c)
+            N.check(lib.dppo_gru_plan(ctypes.byref(_dims(G, D, A, T=T, Nn=Nn)), out),
+                    "dppo_gru_plan")
+            assert out[0] == E and out[1] == len(wgs) and sum(ne for ne, _ in wgs) == Nn
+            full |= {c.shape for ne, S in wgs if ne == E and S > 256}
+            partial |= {c.shape for ne, S in wgs if ne < E and S > 256}
+            three |= {c.shape for ne, S in wgs if S > 512}
+            exact |= {c.shape for ne, S in wgs if S == 256}
+            slabs |= {c.shape for _ in wgs[100:]}
+        default = W.config(G)
+        assert (default.rollout_steps, default.num_envs) in {c.shape[:2] for c in cases}
+        assert bool(exact) == (default.rollout_steps * E == 256)
+        for what in (full, partial, three, slabs):
+            assert what, (G, full, partial, three, slabs)
+            for shape in what:   # each off-policy at both fractions and on-policy at 1.0
+                runs = {(c.frac, c.on_policy) for c in cases
+                        if c.shape == shape and c.dones == "random"}
+                assert runs == {(1.0, False), (0.4, False), (1.0, True)}, (G, shape, runs)
+        assert W.MANY_ENVS in slabs and W.MANY_ENVS_HEAD % E == 0 and W.MANY_ENVS[1] % E != 0
+        # the carry reset and the prefetch clamps at a T of more than one pass
+        for d in ("env_always", "last"):
+            hit = [c for c in cases if c.dones == d]
+            assert hit and all(S > 256 for c in hit for _, S in W.workgroups(c)[:1])
+            assert all(gru_cases.DONE_ENV < c.shape[1] for c in hit)

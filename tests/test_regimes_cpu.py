@@ -122,10 +122,11 @@ def test_offpolicy_regime_conditions_hold(case):
     _assert_oracles(res, err, R.NEAR_CAP, L, names)
 
 
-@pytest.mark.parametrize("case", R.GRU_CASES, ids=str)
+@pytest.mark.parametrize("case", R.GRU_CASES + R.GRU_WIDE_CASES, ids=str)
 def test_gru_regime_is_reached_and_float32_oracle_meets_its_cap(case):
     import torch
-    params, x, mb_idx, m_total = gru_cases.build(case)
+    params, x, mb_idx, m_total = R.gru_build(case)
+    assert params["gru.weight_hh_l0"].shape[1] == x["hx0"].shape[1] == getattr(case, "G", 16)
     edge, share = gru_cases.guards(case, params, x, mb_idx)
     res, err = R.gru_oracle_pair(case, params, x, mb_idx, m_total)
     r = R.gru_reached(params, x)
@@ -144,7 +145,15 @@ def test_gru_regime_is_reached_and_float32_oracle_meets_its_cap(case):
         assert res[torch.float64][0][1] / m_total >= 1e3     # the value loss
     for dt, (sums, g) in res.items():
         assert np.isfinite(sums).all() and all(np.isfinite(t).all() for t in g.values()), dt
-    assert err <= R.NEAR_CAP, err
+    if R.gru_is_far(case):
+        # float32 itself degrades: on-policy only, held to the far cap -- and so is the float32
+        # oracle with its weights an ulp away, or the row was a lucky draw of a chaotic map
+        nudged = R.gru_oracle32_nudged(case, params, x, mb_idx, m_total)
+        print(f"{case}: err_oracle32 nudged {nudged}")
+        assert case.on_policy and name == "hidden6"
+        assert R.NEAR_CAP < err <= R.FAR_CAP and max(nudged) <= R.FAR_CAP, (err, nudged)
+    else:
+        assert err <= R.NEAR_CAP, err
 
 
 @pytest.mark.parametrize("case", R.sampler_cases(), ids=R.case_id)
@@ -169,14 +178,28 @@ def test_sampler_inputs(case):
             assert np.median(p.max(1)) > 0.9
 
 
-@pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
-@pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
-def test_gru_sampler_inputs(regime, D, A):
-    params, obs, dones, hx, nobs = R.gru_sampler_inputs(regime, D, A)
+def _gru_sampler_inputs(regime, D, A, G):
+    params, obs, dones, hx, nobs = R.gru_sampler_inputs(regime, D, A, G)
+    assert hx.shape == (R.SAMPLER_N, G) and params["gru.weight_hh_l0"].shape == (3 * G, G)
     lg = R.gru_step_logits(params, obs, dones, hx)
     want, clear = W.categorical_oracle(lg, R.SEED, R.COUNTER, philox4x32_10, u01)
     assert np.isfinite(lg).all()
     assert clear.mean() >= W.MIN_CLEAR, clear.mean()
+    if regime.startswith("peaked"):     # the scale of the gradient case carries over to one step
+        assert (lg.max(1) - lg.min(1)).max() >= (20 if regime == "peaked20" else 30)
+
+
+@pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
+@pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
+def test_gru_sampler_inputs(regime, D, A):
+    _gru_sampler_inputs(regime, D, A, gru_cases.G)
+
+
+@pytest.mark.parametrize("G", R.gru_wide_cases.WIDTHS)
+@pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
+@pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
+def test_gru_wide_sampler_inputs(regime, D, A, G):
+    _gru_sampler_inputs(regime, D, A, G)
 
 
 @pytest.mark.parametrize("shape", R.LEARN_SHAPES, ids=R.shape_id)
@@ -218,6 +241,14 @@ def test_tables_cover_every_path_and_class():
     assert [r.name for r in R.REGIMES.values() if r.far] == ["obs1000", "peaked60", "combined"]
     assert set(R.OFFPOLICY_S) == {(r.name, R.shape_id(s)) for r, s in R.mlp_cases(R.NEAR)}
     # the existing GRU cases keep their ids and inputs: every regime field defaults to identity
-    for c in gru_cases.CASES:
-        assert (c.obs_scale, c.gru_scale, c.actor_scale, c.ret_scale, c.old_noise,
-                c.seed_shift) == (1.0, 1.0, 1.0, 1.0, 0.0, 0)
+    for c in gru_cases.CASES + R.gru_wide_cases.CASES + R.gru_wide_cases.LONG_CASES:
+        assert (c.obs_scale, c.gru_scale, c.actor_scale, c.ret_scale, c.old_noise) \
+            == (1.0, 1.0, 1.0, 1.0, 0.0)
+        assert c.seed_shift == R.gru_wide_cases.SEED_SHIFT.get((getattr(c, "G", 16), c.name), 0)
+    # the wide regime table: both widths on both shapes, all five regimes, the far rows on-policy
+    assert set(R.GRU_WIDE_REGIMES) == {(g, s) for g in R.gru_wide_cases.WIDTHS
+                                       for s in R.GRU_SHAPES}
+    assert all(set(row) == set(R.GRU_REGIMES) for row in R.GRU_WIDE_REGIMES.values())
+    assert all(r == "hidden6" for r, _, _ in R.GRU_WIDE_FAR)
+    assert len(R.GRU_WIDE_CASES) == 2 * 20 - len(R.GRU_WIDE_FAR)
+    assert all(not R.gru_is_far(c) for c in R.GRU_CASES)
