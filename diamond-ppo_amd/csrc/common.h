@@ -471,6 +471,18 @@ struct GruScratch {
   float *obs, *x1, *gi, *hi, *ho, *r, *z, *n, *ghn, *ya, *yc, *dl, *dv, *dya, *dyc, *dho, *dgi,
       *dgh, *dx1;
 };
+// The gradient kernels' argument (gru_grad_kernel and gruw_grad_kernel<G>: one kernarg layout)
+struct GruArgs {
+  GruOffsets po;
+  const float* params;
+  dppo_gru_batch b;
+  const float* wmask;  // [B] 1 for the minibatch's samples, else 0
+  int T, N, D, D16, A;
+  float inv_m, clip_eps, vf, ent;
+  GruScratch sc;
+  float* slabs;
+  int64_t slab_stride, p_total;
+};
 // G = gru_hidden: 16 runs gru_grad_kernel, 32 and 64 the wide kernel (gruwide.hip); the scratch
 // rows, the envs per workgroup (= samples per gradient slab / T) and the LDS image follow G.
 size_t gru_lds_bytes(int D, int G);
@@ -480,14 +492,11 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
                     const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
                     int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
                     float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s);
-// gruwide.hip: the gradient kernel at G = 32 / 64 (wmask already built by launch_gru_grad)
+// gruwide.hip: the gradient kernel at G = 32 / 64 (a filled, wmask built, by launch_gru_grad)
 bool gruw_width(int G);
 int gruw_envs(int G);
 size_t gruw_lds_bytes(int D, int G);
-int launch_gruw_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
-                     const float* wmask, int T, int N, int D, int A, float inv_m, float clip_eps,
-                     float vf, float ent, const GruScratch& sc, float* slabs, int64_t slab_stride,
-                     int64_t p_total, hipStream_t s);
+int launch_gruw_grad(int G, const GruArgs& a, hipStream_t s);
 
 // The GRU kernels' gate non-linearities (gru.hip learn, gruact.hip rollout: the same bits)
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
@@ -496,20 +505,16 @@ __device__ __forceinline__ float tanh_acc(float x) {
   return 1.0f - 2.0f / (__expf(2.0f * x) + 1.0f);
 }
 
-// RecurrentPPO rollout step (gruact.hip): one GRU step per env from hx, then either both heads,
-// the Categorical draw and its log-prob (launch_gru_act; logits optional) or the critic head
-// alone (launch_gru_value; dones optional, the new hidden state discarded).  n > 0.
-int launch_gru_act(const GruOffsets& po, const float* params, const dppo_gru_step& st, int64_t n,
-                   int D, int A, uint64_t seed, uint64_t counter, hipStream_t s);
-int launch_gru_value(const GruOffsets& po, const float* params, const float* obs, const float* hx,
-                     const uint8_t* dones, int64_t n, int D, float* values, hipStream_t s);
-// the same two steps at G = 32 / 64 (gruactwide.hip): same arguments, outputs and Philox stream
-int gruw_act_envs();  // envs per workgroup
-int launch_gruw_act(int G, const GruOffsets& po, const float* params, const dppo_gru_step& st,
-                    int64_t n, int D, int A, uint64_t seed, uint64_t counter, hipStream_t s);
-int launch_gruw_value(int G, const GruOffsets& po, const float* params, const float* obs,
-                      const float* hx, const uint8_t* dones, int64_t n, int D, float* values,
-                      hipStream_t s);
+// RecurrentPPO rollout step (gruact.hip, G = gru_hidden 16 / 32 / 64): one GRU step per env from
+// hx, then either both heads, the Categorical draw and its log-prob (launch_gru_act; logits
+// optional) or the critic head alone (launch_gru_value; dones optional, the new hidden state
+// discarded).  n > 0.  Same arguments, outputs and Philox stream at every width.
+int gru_act_envs();  // envs per workgroup
+int launch_gru_act(int G, const GruOffsets& po, const float* params, const dppo_gru_step& st,
+                   int64_t n, int D, int A, uint64_t seed, uint64_t counter, hipStream_t s);
+int launch_gru_value(int G, const GruOffsets& po, const float* params, const float* obs,
+                     const float* hx, const uint8_t* dones, int64_t n, int D, float* values,
+                     hipStream_t s);
 
 // Fisher-Yates resolution (shuffle.hip): perms[c][n] from swap targets[c][n]; scratch of
 // scratch_ints >= 3 * count * n int32 (perm_scratch_ints: the size at which the partitioned

@@ -24,9 +24,10 @@
 //     (v_mfma_f32_16x16x4_f32, k = sample) in a fixed order; bias sums on VALU; one slab per
 //     workgroup (optim.hip's slab reduction sums them in a fixed order: bit-reproducible).
 //
-// gru_grad_kernel is the G = 16 kernel.  G = 32 and 64 run gruwide.hip's kernel (same phases and
-// scratch contract, another mapping) and gruactwide.hip's rollout steps; the host code below
-// (validation, layout, workspace, C ABI) serves all three widths and dispatches on G.
+// gru_grad_kernel is the G = 16 kernel.  G = 32 and 64 run gruwide.hip's kernel (same phases,
+// scratch contract and argument struct, another mapping); the rollout steps of all three widths
+// are gruact.hip's.  The host code below (validation, layout, workspace, C ABI) serves all three
+// widths and dispatches the gradient on G.
 #include <cstring>
 #include <vector>
 
@@ -40,18 +41,6 @@ constexpr int kH = 64;        // MLP hidden
 constexpr int kEnvs = 16;     // envs per workgroup
 constexpr int kThr = 256;
 constexpr int kAPad = 16;     // action dims padded
-
-struct GruArgs {
-  GruOffsets po;
-  const float* params;
-  dppo_gru_batch b;
-  const float* wmask;  // [B] 1 for the minibatch's samples, else 0
-  int T, N, D, D16, A;
-  float inv_m, clip_eps, vf, ent;
-  GruScratch sc;
-  float* slabs;
-  int64_t slab_stride, p_total;
-};
 
 // LDS image of the weights (floats)
 struct GruLds {
@@ -554,9 +543,6 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
     DPPO_LAUNCH(mask_kernel, dim3(g), dim3(256), 0, s, idx, m, wmask);
     DPPO_LAUNCH_CHECK();
   }
-  if (G != kG)
-    return launch_gruw_grad(G, po, params, b, wmask, T, N, D, A, inv_m, clip_eps, vf, ent, sc,
-                            slabs, slab_stride, p_total, s);
   GruArgs a{};
   a.po = po;
   a.params = params;
@@ -575,6 +561,7 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
   a.slabs = slabs;
   a.slab_stride = slab_stride;
   a.p_total = p_total;
+  if (G != kG) return launch_gruw_grad(G, a, s);
   const size_t lds = gru_lds_bytes(D, kG);
   const int grid = gru_grid(N, kG);
   DPPO_LAUNCH(gru_grad_kernel, dim3(grid), dim3(kThr), lds, s, a);
@@ -819,11 +806,8 @@ int dppo_gru_act_f32(dppo_gru_handle* h, const float* params, const dppo_gru_ste
   if (n == 0) return DPPO_OK;
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   GruTimed timed(h, 0);
-  if (h->dims.gru_hidden != kG)
-    return launch_gruw_act(h->dims.gru_hidden, h->po, params, *step, n, h->dims.obs_dim,
-                           h->dims.act_dim, seed, counter, (hipStream_t)stream);
-  return launch_gru_act(h->po, params, *step, n, h->dims.obs_dim, h->dims.act_dim, seed, counter,
-                        (hipStream_t)stream);
+  return launch_gru_act(h->dims.gru_hidden, h->po, params, *step, n, h->dims.obs_dim,
+                        h->dims.act_dim, seed, counter, (hipStream_t)stream);
 }
 
 int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs,
@@ -837,11 +821,8 @@ int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs
   if (n == 0) return DPPO_OK;
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   GruTimed timed(h, 1);
-  if (h->dims.gru_hidden != kG)
-    return launch_gruw_value(h->dims.gru_hidden, h->po, params, obs, hx, dones, n,
-                             h->dims.obs_dim, values, (hipStream_t)stream);
-  return launch_gru_value(h->po, params, obs, hx, dones, n, h->dims.obs_dim, values,
-                          (hipStream_t)stream);
+  return launch_gru_value(h->dims.gru_hidden, h->po, params, obs, hx, dones, n, h->dims.obs_dim,
+                          values, (hipStream_t)stream);
 }
 
 int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out) {
@@ -855,7 +836,7 @@ int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out) {
   out[0] = gru_envs(G);
   out[1] = gru_grid(dims->num_envs, G);
   out[2] = (int32_t)gru_lds_bytes(dims->obs_dim, G);
-  out[3] = G == kG ? 4 : gruw_act_envs();  // gruact.hip: one wave of 4 envs
+  out[3] = gru_act_envs();
   return DPPO_OK;
 }
 

@@ -31,18 +31,6 @@ constexpr int kThr = 256;
 constexpr int kAPad = 16;  // action dims padded
 constexpr int kGiBlk = 48; // gate rows per register block of phase A (= gru.hip's 3 G)
 
-struct GruwArgs {
-  GruOffsets po;
-  const float* params;
-  dppo_gru_batch b;
-  const float* wmask;  // [B] 1 for the minibatch's samples, else 0
-  int T, N, D, D16, A;
-  float inv_m, clip_eps, vf, ent;
-  GruScratch sc;
-  float* slabs;
-  int64_t slab_stride, p_total;
-};
-
 // LDS (floats): the phase's weights at W, then the biases, then the exchange buffers
 struct GruwLds {
   int W, bb, bih, bhh, ba1, ba2, bc1, Wc2, bc2, hbuf, gbuf, red, total;
@@ -121,7 +109,7 @@ __device__ __forceinline__ f32x4 tile_sum(const float* __restrict__ A, int lda, 
 }
 
 template <int G>
-__global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruwArgs a) {
+__global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
   constexpr int kEnvs = kThr / G, G3 = 3 * G, kWs = G + 1;
   static_assert(G3 % kGiBlk == 0 && G3 <= kThr && G % 16 == 0, "gate blocking");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -610,7 +598,7 @@ __global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruwArgs a) {
 }
 
 template <int G>
-int launch_g(const GruwArgs& a, hipStream_t s) {
+int launch_g(const GruArgs& a, hipStream_t s) {
   static const bool attr = [] {
     raise_dyn_lds((const void*)gruw_grad_kernel<G>);
     return true;
@@ -631,28 +619,7 @@ int gruw_envs(int G) { return kThr / G; }
 
 size_t gruw_lds_bytes(int D, int G) { return (size_t)gruw_lds(D, G).total * sizeof(float); }
 
-int launch_gruw_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
-                     const float* wmask, int T, int N, int D, int A, float inv_m, float clip_eps,
-                     float vf, float ent, const GruScratch& sc, float* slabs, int64_t slab_stride,
-                     int64_t p_total, hipStream_t s) {
-  GruwArgs a{};
-  a.po = po;
-  a.params = params;
-  a.b = b;
-  a.wmask = wmask;
-  a.T = T;
-  a.N = N;
-  a.D = D;
-  a.D16 = (D + 15) / 16 * 16;
-  a.A = A;
-  a.inv_m = inv_m;
-  a.clip_eps = clip_eps;
-  a.vf = vf;
-  a.ent = ent;
-  a.sc = sc;
-  a.slabs = slabs;
-  a.slab_stride = slab_stride;
-  a.p_total = p_total;
+int launch_gruw_grad(int G, const GruArgs& a, hipStream_t s) {
   if (G == 32) return launch_g<32>(a, s);
   if (G == 64) return launch_g<64>(a, s);
   set_error("no wide GRU gradient kernel for gru_hidden=%d", G);

@@ -1,5 +1,5 @@
 // Philox4x32-10 and the u32 -> (0, 1) map of the rollout samplers (mlp.hip act_kernel,
-// gruact.hip gru_act_kernel): one definition, so every sampler draws the documented stream
+// gruact.hip gru_act_kernel<G> at every GRU width): one definition, so every sampler draws the documented stream
 // (tests restate it in NumPy).
 #pragma once
 

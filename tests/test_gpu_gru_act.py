@@ -1,5 +1,6 @@
 """RecurrentPPO's fused rollout step (csrc/gruact.hip: dppo_gru_act_f32 / dppo_gru_value_f32,
-SURVEY §8 f4 rollout) and the rollout() path built on it (RecurrentPPO.fused_rollout).
+SURVEY §8 f4 rollout) and the rollout() path built on it (RecurrentPPO.fused_rollout), at the
+default gru_hidden_dim 16; the helpers take the width (tests/test_gpu_gru_wide_act.py: 32, 64).
 
 Yardstick: ``RecurrentActorCriticNetwork(...).double()`` on the CPU with the agent's parameters
 (tests/test_gru_oracle_cpu.py pins it to oracle/gru_torch.py; the reference itself crashes at
@@ -27,14 +28,15 @@ G = 16
 ATOL, RTOL = 2e-5, 1e-5
 
 
-def _agent(T, Nn, D, A, spread=True, **kw):
+def _agent(T, Nn, D, A, spread=True, G=G, **kw):
     import gym_stub
     np.random.seed(0)
     torch.manual_seed(0)
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
-    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False, **kw)
+    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
+                                     gru_hidden_dim=G, **kw)
     agent = diamond.RecurrentPPO(None, cfg, envs=envs)
-    assert agent.gru is not None
+    assert agent.gru is not None, "gru_hidden_dim %d did not take the fused path" % G
     if spread:   # spread the weights so gates and heads leave their linear range
         torch.manual_seed(1)
         with torch.no_grad():
@@ -52,7 +54,7 @@ def _oracle_net(agent):
     return net
 
 
-def _inputs(n, D, seed, done_frac=0.3):
+def _inputs(n, D, seed, done_frac=0.3, G=G):
     rng = np.random.default_rng(seed)
     return (rng.standard_normal((n, D)).astype(np.float32),
             rng.random(n) < done_frac,
@@ -66,7 +68,7 @@ def _dev(agent, x, dt=None):
 
 def run_act(agent, obs, dones, hx, seed=1, counter=0, logits=True):
     """One dppo_gru_act_f32 call on host arrays -> dict of host arrays."""
-    n, A, dev = obs.shape[0], agent.gru.dims.act_dim, agent.device
+    n, A, G, dev = obs.shape[0], agent.gru.dims.act_dim, agent.gru.dims.gru_hidden, agent.device
     o, d, h = _dev(agent, obs), _dev(agent, dones, torch.uint8), _dev(agent, hx)
     out = dict(hx_out=torch.empty((n, G), device=dev),
                actions=torch.empty(n, dtype=torch.int32, device=dev),
@@ -264,9 +266,9 @@ def _start(agent, env_seed=7):
     agent.current_hx = torch.zeros(1, cfg.num_envs, cfg.gru_hidden_dim, device=agent.device)
 
 
-def _rollout_agent(T, Nn, D, A, fused, **kw):
+def _rollout_agent(T, Nn, D, A, fused, G=G, **kw):
     import gym_stub
-    agent = _agent(T, Nn, D, A, **kw)
+    agent = _agent(T, Nn, D, A, G=G, **kw)
     # episodes end often enough for several hidden resets inside T steps
     agent.envs = gym_stub.SyncVectorEnv(
         [lambda: gym_stub.SyntheticEnv(D, A, p_term=0.1, p_trunc=0.05)] * Nn)

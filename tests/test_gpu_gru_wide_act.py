@@ -1,7 +1,8 @@
-"""RecurrentPPO's fused rollout step at gru_hidden_dim 32 and 64 (csrc/gruactwide.hip behind
-dppo_gru_act_f32 / dppo_gru_value_f32) and the rollout() path on it: tests/test_gpu_gru_act.py's
-checks with the same yardstick (the float64 CPU module), the same bounds (atol 2e-5, rtol 1e-5)
-and the same NumPy restatement of the Philox stream, which must not depend on G."""
+"""RecurrentPPO's fused rollout step at gru_hidden_dim 32 and 64 (csrc/gruact.hip's kernels at
+G = 32 / 64 behind dppo_gru_act_f32 / dppo_gru_value_f32) and the rollout() path on it:
+tests/test_gpu_gru_act.py's checks and helpers with the same yardstick (the float64 CPU module),
+the same bounds (atol 2e-5, rtol 1e-5) and the same NumPy restatement of the Philox stream, which
+must not depend on G."""
 import ctypes
 
 import numpy as np
@@ -10,12 +11,12 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-import diamond
 from diamond import _native as N
 from oracle import gru_torch as GT
 
-from test_gpu_gru_act import (ATOL, M32, RTOL, _dev, _oracle_net, _start, log_softmax64,
-                              oracle_step, oracle_value, run_value)
+import test_gpu_gru_act as base
+from test_gpu_gru_act import (ATOL, M32, RTOL, _inputs, _oracle_net, log_softmax64, oracle_step,
+                              oracle_value, run_act, run_value)
 from test_gpu_rollout_ckpt import philox4x32_10, u01
 
 WIDTHS = (32, 64)
@@ -24,51 +25,12 @@ ENVS_PER_WG = 4     # both widths (dppo_gru_plan out[3], checked below)
 _agents = {}
 
 
-def _agent(G, D, A, T=2, Nn=4, spread=True, cache=True, **kw):
-    import gym_stub
+def _agent(G, D, A, T=2, Nn=4, spread=True):
+    """test_gpu_gru_act's agent at width G, one per key for the whole module."""
     key = (G, D, A, T, Nn, spread)
-    if cache and not kw and key in _agents:
-        return _agents[key]
-    np.random.seed(0)
-    torch.manual_seed(0)
-    envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
-    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
-                                     gru_hidden_dim=G, **kw)
-    agent = diamond.RecurrentPPO(None, cfg, envs=envs)
-    assert agent.gru is not None, "gru_hidden_dim %d did not take the fused path" % G
-    if spread:   # spread the weights so gates and heads leave their linear range
-        torch.manual_seed(1)
-        with torch.no_grad():
-            for p in agent.network.parameters():
-                p.add_(torch.randn_like(p) * 0.3)
-    if cache and not kw:
-        _agents[key] = agent
-    return agent
-
-
-def _inputs(n, D, G, seed, done_frac=0.3):
-    rng = np.random.default_rng(seed)
-    return (rng.standard_normal((n, D)).astype(np.float32),
-            rng.random(n) < done_frac,
-            (rng.standard_normal((n, G)) * 0.5).astype(np.float32))
-
-
-def run_act(agent, obs, dones, hx, seed=1, counter=0, logits=True):
-    """One dppo_gru_act_f32 call on host arrays -> dict of host arrays."""
-    n, A, G, dev = obs.shape[0], agent.gru.dims.act_dim, agent.gru.dims.gru_hidden, agent.device
-    o, d, h = _dev(agent, obs), _dev(agent, dones, torch.uint8), _dev(agent, hx)
-    out = dict(hx_out=torch.empty((n, G), device=dev),
-               actions=torch.empty(n, dtype=torch.int32, device=dev),
-               log_probs=torch.empty(n, device=dev), values=torch.empty(n, device=dev),
-               logits=torch.empty((n, A), device=dev) if logits else None)
-    step = N.GruStep(o.data_ptr(), d.data_ptr(), h.data_ptr(), out["hx_out"].data_ptr(),
-                     out["actions"].data_ptr(), out["log_probs"].data_ptr(),
-                     out["values"].data_ptr(), out["logits"].data_ptr() if logits else None)
-    N.check(agent.gru.lib.dppo_gru_act_f32(
-        agent.gru.h, agent.flat.flat.data_ptr(), ctypes.byref(step), n, seed, counter,
-        torch.cuda.current_stream().cuda_stream), "dppo_gru_act_f32")
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+    if key not in _agents:
+        _agents[key] = base._agent(T, Nn, D, A, spread=spread, G=G)
+    return _agents[key]
 
 
 # ---- 1. one step against the float64 module
@@ -81,7 +43,7 @@ def test_one_step_matches_float64_module(G, n, D, A):
     N.check(agent.gru.lib.dppo_gru_plan(ctypes.byref(agent.gru.dims), plan), "dppo_gru_plan")
     assert plan[3] == ENVS_PER_WG
     net = _oracle_net(agent)
-    obs, mixed, hx = _inputs(n, D, G, seed=n * 10 + A)
+    obs, mixed, hx = _inputs(n, D, seed=n * 10 + A, G=G)
     nobs = np.random.default_rng(n).standard_normal((n, D)).astype(np.float32)
     close = lambda got, want, what: np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL,
                                                                err_msg=what)
@@ -118,7 +80,7 @@ def test_draws_are_the_documented_philox_stream(G):
     n, D, A = 4101, 8, 16
     agent = _agent(G, D, A)
     net = _oracle_net(agent)
-    obs, dones, hx = _inputs(n, D, G, seed=11)
+    obs, dones, hx = _inputs(n, D, seed=11, G=G)
     seed, counter = 0x1234_5678_9ABC_DEF1, 77
     got = run_act(agent, obs, dones, hx, seed, counter)
     lg, _, _ = oracle_step(net, obs, dones, hx)
@@ -147,7 +109,7 @@ def test_draws_are_the_documented_philox_stream(G):
 def test_outputs_do_not_depend_on_batch_size_or_position(G):
     n, D, A = 4101, 8, 4
     agent = _agent(G, D, A)
-    obs, dones, hx = _inputs(n, D, G, seed=21)
+    obs, dones, hx = _inputs(n, D, seed=21, G=G)
     big = run_act(agent, obs, dones, hx, seed=2, counter=5)
     small = run_act(agent, obs[:3], dones[:3], hx[:3], seed=2, counter=5)
     for k in big:   # same sample indices: the draw and its log-prob agree too
@@ -164,14 +126,7 @@ def test_outputs_do_not_depend_on_batch_size_or_position(G):
 
 # ---- 4. the rollout on it
 def _rollout_agent(G, T, Nn, D, A, fused, **kw):
-    import gym_stub
-    agent = _agent(G, D, A, T=T, Nn=Nn, cache=False, **kw)
-    # episodes end often enough for several hidden resets inside T steps
-    agent.envs = gym_stub.SyncVectorEnv(
-        [lambda: gym_stub.SyntheticEnv(D, A, p_term=0.1, p_trunc=0.05)] * Nn)
-    agent.fused_rollout = fused
-    _start(agent)
-    return agent
+    return base._rollout_agent(T, Nn, D, A, fused, G=G, **kw)
 
 
 @pytest.mark.parametrize("G", WIDTHS)

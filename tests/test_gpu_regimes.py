@@ -347,11 +347,8 @@ def test_mlp_sampler_in_regime(case):
 
 @functools.lru_cache(maxsize=None)
 def _gru_agent(D, A, G=gru_cases.G):
-    if G != gru_cases.G:
-        from test_gpu_gru_wide_act import _agent as wide_agent
-        return wide_agent(G, D, A, T=2, Nn=4, spread=False)
     from test_gpu_gru_act import _agent
-    return _agent(2, 4, D, A, spread=False)
+    return _agent(2, 4, D, A, spread=False, G=G)
 
 
 def _gru_net(agent, params, dt):
@@ -379,11 +376,7 @@ def _gru_value(net, dt, obs, hx):
 
 
 def _gru_sampler(regime, D, A, G):
-    from test_gpu_gru_act import log_softmax64, run_value
-    if G == gru_cases.G:
-        from test_gpu_gru_act import run_act
-    else:
-        from test_gpu_gru_wide_act import run_act
+    from test_gpu_gru_act import log_softmax64, run_act, run_value
     n = R.SAMPLER_N
     params, obs, dones, hx, nobs = R.gru_sampler_inputs(regime, D, A, G)
     agent = _gru_agent(D, A, G)
@@ -425,7 +418,7 @@ def test_gru_sampler_in_regime(regime, D, A):
 @pytest.mark.parametrize("D,A", R.GRU_SAMPLER_SHAPES)
 @pytest.mark.parametrize("regime", R.GRU_SAMPLER_REGIMES)
 def test_gru_wide_sampler_in_regime(regime, D, A, G):
-    """The same at gru_hidden_dim 32 and 64 (csrc/gruactwide.hip), with GRU_WIDE_REGIMES' scales."""
+    """The same at gru_hidden_dim 32 and 64 (csrc/gruact.hip), with GRU_WIDE_REGIMES' scales."""
     _gru_sampler(regime, D, A, G)
 
 

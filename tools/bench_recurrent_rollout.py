@@ -10,7 +10,7 @@ host hits both alike): `--warmup` untimed rollouts each, then `--rollouts` timed
 bracketed by a device synchronisation and the host wall clock (a rollout is 2-100 ms).  Reported:
 the median ms per rollout() of each path with min / max, and torch / fused.
 `--gru-hidden G [G ...]` (default 16) runs other GRU widths, one after the other; 32 and 64 use
-the kernels of csrc/gruactwide.hip, and a result row of a width other than 16 carries "G":
+csrc/gruact.hip's kernels at G = 32 / 64, and a result row of a width other than 16 carries "G":
 
     python tools/bench_recurrent_rollout.py --gru-hidden 32 64 \
         --out profiles/recurrent_wide_rollout.json
