@@ -1,5 +1,6 @@
 """Shared helpers of the GPU test modules (synthetic rollouts, random default-network parameters,
-C-ABI hyper-parameters, the off-policy minibatch recipe).  Test infrastructure only.  Nothing here
+C-ABI hyper-parameters, the near-regime element bound, the off-policy minibatch recipe).  Test
+infrastructure only.  Nothing here
 touches the GPU at import; synth_host, random_params and offpolicy_inputs are NumPy plus the oracle
 and also run in the CPU suite."""
 import numpy as np
@@ -77,6 +78,23 @@ def random_params(L, names, D, A, cont, rng):
     for i, n in enumerate(names):
         flat[L.offset[i]:L.offset[i] + L.numel[i]] = params[n].ravel()
     return params, flat
+
+
+def _figures(got, exact, o32):
+    """Of |got - exact| <= 2e-5 max(1, |exact|) + 4 |oracle32 - exact| per element: (max |got -
+    exact|, max |oracle32 - exact|, elements beyond the bound, largest excess over it)."""
+    exact = np.asarray(exact, np.float64)
+    d32 = np.abs(np.asarray(o32, np.float64) - exact)
+    tol = 2e-5 * np.maximum(1.0, np.abs(exact)) + 4 * d32
+    d = np.abs(np.asarray(got, np.float64) - exact)
+    return float(d.max()), float(d32.max()), int((d > tol).sum()), float((d - tol).max())
+
+
+def _within(got, exact, o32, what):
+    figs = _figures(got, exact, o32)
+    assert np.isfinite(got).all(), what
+    assert figs[2] == 0, (what, figs)
+    return figs[:2]
 
 
 def hparams(**over):

@@ -51,7 +51,7 @@ import gpu_helpers as G
 import gru_cases
 import regime_cases as R
 import wide_act_cases as W
-from gpu_helpers import dev, hparams, sample_split, stream, to_device
+from gpu_helpers import _figures, _within, dev, hparams, sample_split, stream, to_device
 from test_gpu_rollout_ckpt import oracle_gaussian_draws, philox4x32_10, u01
 
 _KEYS = ("log_probs", "values", "next_values", "advantages", "returns")
@@ -153,23 +153,6 @@ def test_onpolicy_minibatch_gradient_in_regime(case):
     res, err32 = R.oracle_pair(c["params"], args, P.Hyper(), cont)
     _check_gradient(f"on {R.case_id(case)}", regime.far, c["L"], c["names"], g, loss4, res, err32,
                     FAR_MEASURED.get((regime.name, shape[0])))
-
-
-def _figures(got, exact, o32):
-    """Of |got - exact| <= 2e-5 max(1, |exact|) + 4 |oracle32 - exact| per element: (max |got -
-    exact|, max |oracle32 - exact|, elements beyond the bound, largest excess over it)."""
-    exact = np.asarray(exact, np.float64)
-    d32 = np.abs(np.asarray(o32, np.float64) - exact)
-    tol = 2e-5 * np.maximum(1.0, np.abs(exact)) + 4 * d32
-    d = np.abs(np.asarray(got, np.float64) - exact)
-    return float(d.max()), float(d32.max()), int((d > tol).sum()), float((d - tol).max())
-
-
-def _within(got, exact, o32, what):
-    figs = _figures(got, exact, o32)
-    assert np.isfinite(got).all(), what
-    assert figs[2] == 0, (what, figs)
-    return figs[:2]
 
 
 # combined (far): the per-element bound of b does not hold, in any family.  Measured on an MI355X,
