@@ -462,7 +462,7 @@ struct RankPtrs {
 int launch_rank_sum(const RankPtrs& src, int n, void* out, int64_t count, bool f64,
                     hipStream_t s);
 
-// RecurrentPPO fused minibatch gradient (gru.hip): parameter offsets in the flat layout
+// RecurrentPPO fused minibatch gradient (grugrad.hip): parameter offsets in the flat layout
 // (RecurrentActorCriticNetwork.named_parameters() order) and the per-sample scratch arrays.
 struct GruOffsets {
   int64_t Wb, bb, Wih, Whh, bih, bhh, Wa1, ba1, Wa2, ba2, Wc1, bc1, Wc2, bc2;
@@ -471,7 +471,7 @@ struct GruScratch {
   float *obs, *x1, *gi, *hi, *ho, *r, *z, *n, *ghn, *ya, *yc, *dl, *dv, *dya, *dyc, *dho, *dgi,
       *dgh, *dx1;
 };
-// The gradient kernels' argument (gru_grad_kernel and gruw_grad_kernel<G>: one kernarg layout)
+// gru_grad_kernel<G>'s argument
 struct GruArgs {
   GruOffsets po;
   const float* params;
@@ -483,22 +483,18 @@ struct GruArgs {
   float* slabs;
   int64_t slab_stride, p_total;
 };
-// G = gru_hidden: 16 runs gru_grad_kernel, 32 and 64 the wide kernel (gruwide.hip); the scratch
-// rows, the envs per workgroup (= samples per gradient slab / T) and the LDS image follow G.
+// G = gru_hidden 16 / 32 / 64, one instantiation of gru_grad_kernel<G> each; the scratch rows,
+// the envs per workgroup (= samples per gradient slab / T) and the LDS image follow G.
+// launch_gru_grad builds wmask from idx, fills GruArgs and launches; params 16-byte aligned.
 size_t gru_lds_bytes(int D, int G);
-int gru_envs(int G);         // envs per workgroup
+int gru_envs(int G);         // envs per workgroup = 256 / G
 int gru_grid(int N, int G);  // workgroups = gradient slabs
 int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
                     const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
                     int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
                     float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s);
-// gruwide.hip: the gradient kernel at G = 32 / 64 (a filled, wmask built, by launch_gru_grad)
-bool gruw_width(int G);
-int gruw_envs(int G);
-size_t gruw_lds_bytes(int D, int G);
-int launch_gruw_grad(int G, const GruArgs& a, hipStream_t s);
 
-// The GRU kernels' gate non-linearities (gru.hip learn, gruact.hip rollout: the same bits)
+// The GRU kernels' gate non-linearities (grugrad.hip learn, gruact.hip rollout: the same bits)
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanh_acc(float x) {
   // 1 - 2 / (e^{2x} + 1): saturates cleanly, ~1e-7 absolute

@@ -5,7 +5,7 @@
 // draw, log-prob) and one for V(next_obs) (gru_value_kernel: base, GRU cell, critic head).  Both
 // kernels are templates on the GRU hidden width G, instantiated for 16, 32 and 64.
 //
-// Mapping: G lanes per env (lane j = hidden unit j, gru.hip's phase-B mapping), 4 envs per
+// Mapping: G lanes per env (lane j = hidden unit j, grugrad.hip's phase-B mapping), 4 envs per
 // workgroup (4 G threads: one wave at G = 16, 2 at G = 32, 4 at G = 64); an env never straddles a
 // wave.  Lane j computes base features j + G q and head features j + G q (q < 64 / G), the three
 // gate rows j, and logit j (A <= 16 <= G); per-env vectors pass between the steps through LDS

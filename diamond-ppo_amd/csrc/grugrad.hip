@@ -1,20 +1,33 @@
-// RecurrentPPO minibatch gradient for GRU hidden widths 32 and 64: gru.hip's phases, scratch
-// contract and determinism contract on a mapping that scales with G.  (G = 16 stays on
-// gru_grad_kernel, whose per-thread gate arrays and register-resident Whh do not stretch: at
-// G = 64 they would be 192-float arrays, and the whole weight image would be 146 KB of LDS.)
+// RecurrentPPO minibatch gradient, fused: the full [T x N] GRU sequence recomputed from the stored
+// initial hidden state (intended semantics of reference diamond/recurrent_ppo.py:301-367: every
+// minibatch re-runs the sequence, :337, and slices its samples, :340-341), the PPO loss on the
+// minibatch's samples, and the analytic backward through heads, GRU (BPTT with the per-step hidden
+// resets, :82-87) and base layer -- one launch per minibatch instead of torch's hundreds.  The
+// reference itself cannot run (GRUCore.forward evaluates `hx or ...` on a tensor, :78), so the
+// yardstick is torch's own nn.GRU cell on the same semantics (tests/test_gpu_gru.py).
 //
-// One workgroup = 256 / G envs over all T steps (256 threads): 8 envs at G = 32, 4 at G = 64, one
-// gradient slab each.  Phases as in gru.hip, separated by workgroup barriers and exchanging
-// per-sample vectors through the same global scratch (rows sized by G):
-//  A  per sample (thread per sample): x1, then gi = Wih x1 + bih in blocks of 48 gate rows;
+// Network (recurrent_ppo.py:94-149 as restated in diamond/recurrent_ppo.py): x1 = tanh(Wb obs + bb)
+// [64]; torch GRU cell, hidden G: r = s(Wir x1 + bir + Whr h + bhr), z = s(Wiz x1 + biz + Whz h +
+// bhz), n = tanh(Win x1 + bin + r (Whn h + bhn)), h' = (1 - z) n + z h, with h zeroed where the
+// step's prev_done is set; actor Linear(G, 64) tanh Linear(64, A); critic Linear(G, 64) tanh
+// Linear(64, 1).
+//
+// gru_grad_kernel<G> is the one kernel source for G = 16, 32 and 64.  One workgroup = 256 / G envs
+// over all T steps (256 threads): 16 envs at G = 16, 8 at 32, 4 at 64, one gradient slab each.
+// Phases, separated by workgroup barriers, exchanging per-sample vectors through a global scratch
+// (SoA, one row per sample, rows sized by G):
+//  A  per sample (thread per sample): x1, then gi = Wih x1 + bih in blocks of 48 gate rows
+//     (G = 16: the one block beside x1);
 //  B  per env, serial in t: G lanes per env (lane j = hidden unit j, all in one wave), the
 //     recurrent half gh = Whh h + bhh and the cell; Whh read from LDS, h exchanged through LDS;
-//  C  per minibatch sample: heads, loss, head backward -> dL/dh' (h and dh' as G registers);
+//  C  per minibatch sample: heads, loss (ppo.py:264-280 terms), head backward -> dL/dh' (h and
+//     dh' as G registers);
 //  D  per env, serial in reverse: BPTT through the cell, column j of Whh read from LDS;
 //  E  per sample: dx1 = (Wih^T dgi)(1 - x1^2), 64 accumulators, dgi streamed 4 rows at a time;
-//  F  weight gradients on v_mfma_f32_16x16x4_f32 (k = sample) in a fixed order, bias sums on
-//     VALU, one slab per workgroup.
-// No per-thread array is ever indexed by a run-time value.
+//  F  weight gradients = sums over the workgroup's samples of outer products, on
+//     v_mfma_f32_16x16x4_f32 (k = sample) in a fixed order, bias sums on VALU, one slab per
+//     workgroup (optim.hip's slab reduction sums them in a fixed order: bit-reproducible).
+// No per-thread array is ever indexed by a run-time value (that would put it in scratch memory).
 //
 // LDS holds the biases for the whole launch and, in one region restaged between the phases' own
 // barriers, only the weights the current phase reads: A Wb + Wih | B, D Whh | C Wa1 Wc1 Wa2 |
@@ -29,15 +42,15 @@ namespace {
 constexpr int kH = 64;     // MLP hidden
 constexpr int kThr = 256;
 constexpr int kAPad = 16;  // action dims padded
-constexpr int kGiBlk = 48; // gate rows per register block of phase A (= gru.hip's 3 G)
+constexpr int kGiBlk = 48; // gate rows per register block of phase A
 
 // LDS (floats): the phase's weights at W, then the biases, then the exchange buffers
-struct GruwLds {
+struct GruLds {
   int W, bb, bih, bhh, ba1, ba2, bc1, Wc2, bc2, hbuf, gbuf, red, total;
 };
 __host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
-__host__ __device__ constexpr GruwLds gruw_lds(int D, int G) {
-  GruwLds L{};
+__host__ __device__ constexpr GruLds gru_lds(int D, int G) {
+  GruLds L{};
   int o = 0;
   L.W = o;
   o += imax(imax(kH * D + 3 * G * kH, 3 * G * (G + 1)), 2 * kH * G + kAPad * kH);
@@ -68,8 +81,10 @@ __device__ __forceinline__ void stage_whh(float* dst, const float* __restrict__ 
   for (int k = tid; k < 3 * G * G; k += kThr) dst[(k / G) * (G + 1) + (k % G)] = src[k];
 }
 
-// gru.hip's tile_sum: sum over k = samples of A[s][m] B[s][n] for one 16 x 16 output tile; s_k
-// enumerates the workgroup's samples (t, e) as t * N + n0 + e, e < ne, in t-major order.
+// Sum over k = samples of A[s][m] B[s][n] for one 16 x 16 output tile: rows mt*16.., cols nt*16..
+// of arrays with row strides lda / ldb (floats).  Lane (q, r) supplies A[s_{4kk+q}][16mt + r] and
+// B[s_{4kk+q}][16nt + r]; the result D[4q + v][r] lands in register v.  s_k enumerates the
+// workgroup's samples (t, e) as t * N + n0 + e, e < ne, in t-major order.
 // The loads of kSumAhead k-steps are issued together (the loop is bound by their latency), the
 // MFMAs still chain in k order: the same bits as one step at a time.  NE > 0: ne == NE, a
 // compile-time divisor for the full workgroups.
@@ -109,11 +124,11 @@ __device__ __forceinline__ f32x4 tile_sum(const float* __restrict__ A, int lda, 
 }
 
 template <int G>
-__global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
+__global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
   constexpr int kEnvs = kThr / G, G3 = 3 * G, kWs = G + 1;
   static_assert(G3 % kGiBlk == 0 && G3 <= kThr && G % 16 == 0, "gate blocking");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const GruwLds L = gruw_lds(a.D, G);
+  const GruLds L = gru_lds(a.D, G);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = blockIdx.x * kEnvs;
   const int ne = min(kEnvs, a.N - n0);
@@ -143,8 +158,14 @@ __global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
   stage4(Wih, P + po.Wih, G3 * kH, tid);
   __syncthreads();
 
-  // ---- A: x1 (8 features at a time, as gru.hip), then gi in blocks of kGiBlk gate rows with
-  // x1 re-read from the scratch row this thread just wrote
+  // ---- A: x1 (8 features at a time), then gi in blocks of kGiBlk gate rows with x1 re-read
+  // from the scratch row this thread just wrote.  At G = 16 the gates are one block, which
+  // accumulates beside x1 instead (x1 still in registers): the form this width has always had,
+  // kept because the compiler pairs the products of a re-read x1 for its packed instructions
+  // the other way round and so contracts the other product of a pair -- not the same bits.
+  // (The two forms share no helper: passing x1 as eight scalars changes how the blocks of the
+  // wider instantiations are compiled.)
+  constexpr bool kOneBlk = G3 == kGiBlk;
   for (int s = tid; s < S; s += kThr) {
     const int t = s / ne, e = s - t * ne;
     const int64_t i = (int64_t)t * N + n0 + e;
@@ -156,6 +177,11 @@ __global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
 #pragma unroll
       for (int c = 0; c < 32; ++c)
         if (c < a.D16) ob16[c] = ob[c];
+      [[maybe_unused]] float gi[kOneBlk ? kGiBlk : 1];
+      if constexpr (kOneBlk) {
+#pragma unroll
+        for (int g = 0; g < kGiBlk; ++g) gi[g] = lds[L.bih + g];
+      }
 #pragma unroll 1
       for (int o0 = 0; o0 < kH; o0 += 8) {
         float x[8];
@@ -170,30 +196,47 @@ __global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
         f32x4* xo = (f32x4*)(sc.x1 + i * kH + o0);
         xo[0] = (f32x4){x[0], x[1], x[2], x[3]};
         xo[1] = (f32x4){x[4], x[5], x[6], x[7]};
-      }
-    }
-#pragma unroll 1
-    for (int g0 = 0; g0 < G3; g0 += kGiBlk) {
-      float gi[kGiBlk];
+        if constexpr (kOneBlk) {
 #pragma unroll
-      for (int g = 0; g < kGiBlk; ++g) gi[g] = lds[L.bih + g0 + g];
-      const float* wrow = Wih + g0 * kH;
-#pragma unroll 1
-      for (int o0 = 0; o0 < kH; o0 += 8) {
-        const f32x4 xa = *(const f32x4*)(sc.x1 + i * kH + o0);
-        const f32x4 xb = *(const f32x4*)(sc.x1 + i * kH + o0 + 4);
-#pragma unroll
-        for (int g = 0; g < kGiBlk; ++g) {
-          const f32x4 w0 = *(const f32x4*)(wrow + g * kH + o0);
-          const f32x4 w1 = *(const f32x4*)(wrow + g * kH + o0 + 4);
-          gi[g] += ((w0[0] * xa[0] + w0[1] * xa[1]) + (w0[2] * xa[2] + w0[3] * xa[3])) +
-                   ((w1[0] * xb[0] + w1[1] * xb[1]) + (w1[2] * xb[2] + w1[3] * xb[3]));
+          for (int g = 0; g < kGiBlk; ++g) {
+            const f32x4 w0 = *(const f32x4*)(Wih + g * kH + o0);
+            const f32x4 w1 = *(const f32x4*)(Wih + g * kH + o0 + 4);
+            gi[g] += ((w0[0] * x[0] + w0[1] * x[1]) + (w0[2] * x[2] + w0[3] * x[3])) +
+                     ((w1[0] * x[4] + w1[1] * x[5]) + (w1[2] * x[6] + w1[3] * x[7]));
+          }
         }
       }
-      f32x4* go = (f32x4*)(sc.gi + i * G3 + g0);
+      if constexpr (kOneBlk) {
+        f32x4* go = (f32x4*)(sc.gi + i * G3);
 #pragma unroll
-      for (int g = 0; g < kGiBlk / 4; ++g)
-        go[g] = (f32x4){gi[4 * g], gi[4 * g + 1], gi[4 * g + 2], gi[4 * g + 3]};
+        for (int g = 0; g < kGiBlk / 4; ++g)
+          go[g] = (f32x4){gi[4 * g], gi[4 * g + 1], gi[4 * g + 2], gi[4 * g + 3]};
+      }
+    }
+    if constexpr (!kOneBlk) {
+#pragma unroll 1
+      for (int g0 = 0; g0 < G3; g0 += kGiBlk) {
+        float gi[kGiBlk];
+#pragma unroll
+        for (int g = 0; g < kGiBlk; ++g) gi[g] = lds[L.bih + g0 + g];
+        const float* wrow = Wih + g0 * kH;
+#pragma unroll 1
+        for (int o0 = 0; o0 < kH; o0 += 8) {
+          const f32x4 xa = *(const f32x4*)(sc.x1 + i * kH + o0);
+          const f32x4 xb = *(const f32x4*)(sc.x1 + i * kH + o0 + 4);
+#pragma unroll
+          for (int g = 0; g < kGiBlk; ++g) {
+            const f32x4 w0 = *(const f32x4*)(wrow + g * kH + o0);
+            const f32x4 w1 = *(const f32x4*)(wrow + g * kH + o0 + 4);
+            gi[g] += ((w0[0] * xa[0] + w0[1] * xa[1]) + (w0[2] * xa[2] + w0[3] * xa[3])) +
+                     ((w1[0] * xb[0] + w1[1] * xb[1]) + (w1[2] * xb[2] + w1[3] * xb[3]));
+          }
+        }
+        f32x4* go = (f32x4*)(sc.gi + i * G3 + g0);
+#pragma unroll
+        for (int g = 0; g < kGiBlk / 4; ++g)
+          go[g] = (f32x4){gi[4 * g], gi[4 * g + 1], gi[4 * g + 2], gi[4 * g + 3]};
+      }
     }
   }
   __syncthreads();
@@ -260,8 +303,9 @@ __global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
   for (int k = tid; k < kAPad * kH; k += kThr) Wa2[k] = (k >> 6) < A ? P[po.Wa2 + k] : 0.f;
   __syncthreads();
 
-  // ---- C: heads, loss and head backward per sample (ppo.py:264-280 with the GRU features):
-  // gru.hip's phase C with the feature dots running over G
+  // ---- C: heads, loss and head backward per sample (ppo.py:264-280 with the GRU features).
+  // Forward 8 head features at a time (stored, and folded into the logits / value at once);
+  // backward the same blocks re-read from the scratch rows this thread just wrote.
   float s_pi = 0.f, s_v = 0.f, s_ent = 0.f;
   for (int s = tid; s < S; s += kThr) {
     const int t = s / ne, ee = s - t * ne;
@@ -597,33 +641,68 @@ __global__ __launch_bounds__(kThr) void gruw_grad_kernel(GruArgs a) {
   }
 }
 
+__global__ void mask_kernel(const int32_t* __restrict__ idx, int m, float* __restrict__ wmask) {
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < m; k += gridDim.x * blockDim.x)
+    wmask[idx[k]] = 1.0f;
+}
+
 template <int G>
 int launch_g(const GruArgs& a, hipStream_t s) {
   static const bool attr = [] {
-    raise_dyn_lds((const void*)gruw_grad_kernel<G>);
+    raise_dyn_lds((const void*)gru_grad_kernel<G>);
     return true;
   }();
   (void)attr;
-  const size_t lds = (size_t)gruw_lds(a.D, G).total * sizeof(float);
-  const int grid = (a.N + kThr / G - 1) / (kThr / G);
-  DPPO_LAUNCH(gruw_grad_kernel<G>, dim3(grid), dim3(kThr), lds, s, a);
+  DPPO_LAUNCH(gru_grad_kernel<G>, dim3(gru_grid(a.N, G)), dim3(kThr), gru_lds_bytes(a.D, G), s, a);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }
 
 }  // namespace
 
-bool gruw_width(int G) { return G == 32 || G == 64; }
+int gru_envs(int G) { return kThr / G; }
 
-int gruw_envs(int G) { return kThr / G; }
+int gru_grid(int N, int G) { return (N + gru_envs(G) - 1) / gru_envs(G); }
 
-size_t gruw_lds_bytes(int D, int G) { return (size_t)gruw_lds(D, G).total * sizeof(float); }
+size_t gru_lds_bytes(int D, int G) { return (size_t)gru_lds(D, G).total * sizeof(float); }
 
-int launch_gruw_grad(int G, const GruArgs& a, hipStream_t s) {
-  if (G == 32) return launch_g<32>(a, s);
-  if (G == 64) return launch_g<64>(a, s);
-  set_error("no wide GRU gradient kernel for gru_hidden=%d", G);
-  return DPPO_EUNSUPPORTED;
+int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
+                    const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
+                    int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
+                    float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s) {
+  DPPO_HIP_CHECK(hipMemsetAsync(wmask, 0, (size_t)B * sizeof(float), s));
+  if (m > 0) {
+    int g = (m + 255) / 256;
+    if (g > 1024) g = 1024;
+    DPPO_LAUNCH(mask_kernel, dim3(g), dim3(256), 0, s, idx, m, wmask);
+    DPPO_LAUNCH_CHECK();
+  }
+  GruArgs a{};
+  a.po = po;
+  a.params = params;
+  a.b = b;
+  a.wmask = wmask;
+  a.T = T;
+  a.N = N;
+  a.D = D;
+  a.D16 = (D + 15) / 16 * 16;
+  a.A = A;
+  a.inv_m = inv_m;
+  a.clip_eps = clip_eps;
+  a.vf = vf;
+  a.ent = ent;
+  a.sc = sc;
+  a.slabs = slabs;
+  a.slab_stride = slab_stride;
+  a.p_total = p_total;
+  switch (G) {
+    case 16: return launch_g<16>(a, s);
+    case 32: return launch_g<32>(a, s);
+    case 64: return launch_g<64>(a, s);
+    default:
+      set_error("no GRU gradient kernel for gru_hidden=%d", G);
+      return DPPO_EUNSUPPORTED;
+  }
 }
 
 }  // namespace dppo

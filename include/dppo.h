@@ -466,7 +466,7 @@ int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out);
  * idx[0..m) (flat t * N + n), divided by m_total (the global minibatch size), and the analytic
  * backward through time.  grad [layout.total + 8]: the summed gradient in the flat layout, then
  * the loss sums {policy, value, entropy} (divide by m_total).  Stream-ordered, deterministic.
- * For gru_hidden > 16 params must be 16-byte aligned. */
+ * params must be 16-byte aligned at every width (the kernel stages weights with 16-byte loads). */
 int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
                                 const dppo_gru_batch* batch, const int32_t* idx, int32_t m,
                                 int32_t m_total, const dppo_hparams* hp, float* grad,

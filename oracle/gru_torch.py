@@ -4,7 +4,7 @@ semantics of reference diamond/recurrent_ppo.py.  TEST INFRASTRUCTURE ONLY.
 The reference cannot run (GRUCore.forward evaluates ``hx or torch.zeros(...)`` and
 ``dones or ...`` on multi-element tensors, recurrent_ppo.py:78-79, raising RuntimeError for every
 num_envs: SURVEY.md §3.5, §8(c)), so no golden trace exists.  This restates what its code says it
-does, evaluated in float64 with autograd as the yardstick of the fused HIP kernel (gru.hip):
+does, evaluated in float64 with autograd as the yardstick of the fused HIP kernel (grugrad.hip):
 
 * ``RecurrentActorCriticNetwork`` (:94-149): base Linear(D, 64) + tanh; ``GRUCore`` (:41-91) = a
   torch GRU cell stepped over t with the hidden state zeroed where ``dones[t]`` (:82-87);

@@ -277,7 +277,7 @@ GRU_CASES = [gru_cases.Case(f"{r}-{'x'.join(map(str, s))}-{'on' if on else 'off'
 
 
 # ---------------------------------------------------------------------------------------------
-# The same five regimes at gru_hidden_dim 32 and 64 (csrc/gruwide.hip, csrc/gruact.hip), through
+# The same five regimes at gru_hidden_dim 32 and 64 (csrc/grugrad.hip, csrc/gruact.hip), through
 # gru_wide_cases.Case.  The G = 16 scales do not carry over: the heads read 32 / 64 hidden units, so
 # the same actor_scale gives gaps of 65 to 157, and the recurrent map at gru_scale 5 - 6 is chaotic
 # at these widths (the float32 autograd oracle itself ends 7e-5 .. 2e-2 of max|g| from the float64

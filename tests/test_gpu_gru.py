@@ -1,4 +1,4 @@
-"""The fused RecurrentPPO minibatch kernel (csrc/gru.hip, dppo_gru_minibatch_grad_f32; SURVEY §8
+"""The fused RecurrentPPO minibatch kernel (csrc/grugrad.hip, dppo_gru_minibatch_grad_f32; SURVEY §8
 f4) against the float64 autograd restatement of the reference's intended semantics
 (oracle/gru_torch.py: recurrent_ppo.py:41-91, :301-367; the reference itself crashes at :78, so
 no golden trace exists).

@@ -1,9 +1,10 @@
-"""The fused RecurrentPPO minibatch kernel at gru_hidden_dim 32 and 64 (csrc/gruwide.hip behind
+"""The fused RecurrentPPO minibatch kernel per width (csrc/grugrad.hip behind
 dppo_gru_minibatch_grad_f32) against the float64 autograd oracle (oracle/gru_torch.py), on the
-cases of tests/gru_wide_cases.py: tests/gru_cases.py's edge cases rebuilt per G, plus env counts
-around the kernel's envs per workgroup (8 at G = 32, 4 at G = 64), plus LONG_CASES: workgroups whose
-T * ne samples take two and three passes of the 256 threads (full and partial ones), the class
-default shape, and 1030 envs (129 / 258 gradient slabs), under the same bounds.
+cases of tests/gru_wide_cases.py: at gru_hidden_dim 32 and 64 tests/gru_cases.py's edge cases
+rebuilt per G; env counts around the kernel's envs per workgroup (16 at G = 16, 8 at G = 32, 4 at
+G = 64); and LONG_CASES: workgroups whose T * ne samples take two and three passes of the 256
+threads (full and partial ones), S = 256 exactly, and 1030 envs (65 / 129 / 258 gradient slabs),
+under the same bounds.  (G = 16 on gru_cases.CASES themselves: tests/test_gpu_gru.py.)
 
 Tolerances, the project's bound for this kernel (tests/test_gpu_gru.py): per tensor
 max|diff| <= 2e-5 x max|g|, loss sums rtol 1e-5 and atol 1e-5 m.  Every case also checks that the

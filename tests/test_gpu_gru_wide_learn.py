@@ -4,7 +4,7 @@ comparisons and tolerances of tests/test_gpu_gru_learn.py on (T, N, D, A) = (8, 
 gradient kernel's 256 threads take in one pass -- (40, 9, 6, 3) at 32, (72, 5, 6, 3) at 64, each
 with a 1-env last workgroup -- with 2 epochs x 3 minibatches; two learn() calls under a decaying
 LR (8 / 12 Adam steps at lr <= 3e-4).  Both of the agent's paths -- the fused kernel
-(fused_gru=True, csrc/gruwide.hip) and torch autograd (fused_gru=False) -- are compared with the
+(fused_gru=True, csrc/grugrad.hip) and torch autograd (fused_gru=False) -- are compared with the
 oracle; then with each other under the bound of test_recurrent_learn_fused_matches_torch_path.
 
 Per learn() call, fused path: the returns == values + ppo_np.gae bit for bit, the normalised

@@ -240,7 +240,7 @@ def test_offpolicy_minibatch_gradient_in_regime(case):
 def test_gru_minibatch_gradient_in_regime(case):
     from test_gpu_gru import _kernel_grad
     from oracle import gru_torch as GT
-    if hasattr(case, "G"):      # gru_hidden_dim 32 / 64: csrc/gruwide.hip
+    if hasattr(case, "G"):      # gru_hidden_dim 32 / 64: csrc/grugrad.hip
         from test_gpu_gru_wide import _case_agent
     else:
         from test_gpu_gru import _case_agent

@@ -1,8 +1,9 @@
-"""Host-side surface of the fused GRU kernels at gru_hidden_dim 16, 32 and 64 (csrc/gru.hip host
-code, diamond.recurrent_ppo.fused_gru_shape): the flat layout libdppo reports for a G is
+"""Host-side surface of the fused GRU kernels at gru_hidden_dim 16, 32 and 64 (csrc/gru.hip,
+diamond.recurrent_ppo.fused_gru_shape): the flat layout libdppo reports for a G is
 FlatParams' for the network with that G, the Python predicate is the documented set, and the
-clip-regime guards of every wide gradient case (tests/gru_wide_cases.py, the long ones included)
-hold on the float64 oracle alone, and the long cases reach the multi-pass and many-slab code.
+clip-regime guards of every per-width gradient case (tests/gru_wide_cases.py, the long ones and
+the G = 16 ones included) hold on the float64 oracle alone, and the long cases reach the
+multi-pass and many-slab code.
 The kernels themselves: tests/test_gpu_gru_wide.py, tests/test_gpu_gru_wide_act.py."""
 import ctypes
 import itertools
@@ -74,7 +75,8 @@ def test_envs_per_workgroup():
     lib = N.load()
     assert "dppo_gru_plan" in N.EXPORTED
     out = (ctypes.c_int32 * 4)()
-    for G, E in ((16, 16), *W.ENVS_PER_WG.items()):
+    assert set(W.ENVS_PER_WG) == {16, *W.WIDTHS}
+    for G, E in W.ENVS_PER_WG.items():
         for Nn in (1, E - 1, E, E + 1, 2 * E + 1, 8192):
             if Nn < 1:
                 continue
@@ -94,6 +96,14 @@ def test_case_list_covers_the_issue():
         assert {(7, n, 5, 3) for n in (E - 1, E, E + 1, 2 * E + 1)} <= shapes
         assert set(W.KTAIL_SHAPES) <= shapes
         assert all(c.shape[0] <= 12 and c.shape[1] <= 70 for c in W.CASES)
+    # G = 16: the env-count edges only (the rest are gru_cases.CASES), E + 1 among the latter
+    E = W.ENVS_PER_WG[16]
+    edge = [c for c in W.CASES if c.G == 16]
+    assert not {c.shape for c in edge} & {c.shape for c in gru_cases.CASES}
+    assert (7, E + 1, 5, 3) in {c.shape for c in gru_cases.CASES}
+    for n in (E - 1, E, 2 * E + 1):
+        runs = {(c.frac, c.on_policy) for c in edge if c.shape == (7, n, 5, 3)}
+        assert runs == {(1.0, False), (0.4, False), (1.0, True)}, (n, runs)
 
 
 @pytest.mark.parametrize("case", W.CASES, ids=str)
@@ -114,15 +124,19 @@ def test_long_gradient_case_guards_hold(case):
 def test_long_case_list_reaches_multi_pass_and_many_slabs():
     """What LONG_CASES is for, derived from ENVS_PER_WG and the kernel's 256 threads: per G a
     full and a partial workgroup whose S = T * ne samples need a second pass, one that needs a
-    third, more than 100 gradient slabs, and the class default shape (at 8 envs per workgroup S =
-    256 exactly: the last size of one pass) -- and the slab count is the plan's."""
+    third, more than 100 gradient slabs (more than 64 at G = 16), and the class default shape (at
+    8 envs per workgroup S = 256 exactly: the last size of one pass; at G = 16 that is the
+    (16, 16) case, and the default shape is tests/test_gpu_gru_learn.py's) -- and the slab count
+    is the plan's."""
     names = {str(c) for c in W.LONG_CASES}
     assert len(names) == len(W.LONG_CASES) and not names & {str(c) for c in W.CASES}
     known = {s[2:] for s in W.KTAIL_SHAPES}
     lib = N.load()
     out = (ctypes.c_int32 * 4)()
-    for G in W.WIDTHS:
+    assert {c.G for c in W.LONG_CASES} == set(W.ENVS_PER_WG)
+    for G in W.ENVS_PER_WG:
         E = W.ENVS_PER_WG[G]
+        many = 64 if G == 16 else 100
         cases = [c for c in W.LONG_CASES if c.G == G]
         assert all(c.shape[2:] in known for c in cases)
         full, partial, three, exact, slabs = set(), set(), set(), set(), set()
@@ -136,10 +150,13 @@ def test_long_case_list_reaches_multi_pass_and_many_slabs():
             partial |= {c.shape for ne, S in wgs if ne < E and S > 256}
             three |= {c.shape for ne, S in wgs if S > 512}
             exact |= {c.shape for ne, S in wgs if S == 256}
-            slabs |= {c.shape for _ in wgs[100:]}
+            slabs |= {c.shape for _ in wgs[many:]}
         default = W.config(G)
-        assert (default.rollout_steps, default.num_envs) in {c.shape[:2] for c in cases}
-        assert bool(exact) == (default.rollout_steps * E == 256)
+        if G in W.WIDTHS:
+            assert (default.rollout_steps, default.num_envs) in {c.shape[:2] for c in cases}
+            assert bool(exact) == (default.rollout_steps * E == 256)
+        else:
+            assert exact == {(16, 16, 4, 2)}
         for what in (full, partial, three, slabs):
             assert what, (G, full, partial, three, slabs)
             for shape in what:   # each off-policy at both fractions and on-policy at 1.0

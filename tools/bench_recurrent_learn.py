@@ -11,8 +11,7 @@ alternately (whatever else loads the host hits both alike): `--warmup` untimed l
 Reported: the median ms per learn() of each path with min / max, torch / fused, and whether the
 two medians lie inside each other's min-max spread (then neither path is ahead).
 
-G = 16 runs gru_grad_kernel (csrc/gru.hip) and is the anchor beside the wide kernel's rows
-(csrc/gruwide.hip).  With `fused_gru` off an agent runs exactly what it ran before the fused
+All three widths run gru_grad_kernel<G> (csrc/grugrad.hip).  With `fused_gru` off an agent runs exactly what it ran before the fused
 kernel existed for its G.
 """
 import argparse
