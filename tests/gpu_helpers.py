@@ -290,6 +290,13 @@ OFFPOLICY_SHAPES = [
     ("wide", 128, 30, 1, True, 96, {"clip.1": 0.1, "clip.3": 0.1}, False),
     ("wide", 64, 40, 5, False, 96, {"clip.1": 0.2, "clip.3": 0.2}, False),
     ("wide", 64, 128, 16, True, 96, {"clip.1": 0.03, "clip.3": 0.03}, False),
+    # the other four reachable wide_mb_kernel<H, CONT, NB1> (tests/wide_mb_cases.py INSTANTIATIONS).
+    # Three Gaussian actions starve the below-range regimes under clip 0.3 at s = 0.02 (and nearly
+    # at 0.03); eleven put more than 5 % of the ratios past 16 at s = 0.05 under clip 0.1
+    ("wide", 128, 50, 7, False, 96, {"clip.1": 0.2, "clip.3": 0.2}, False),
+    ("wide", 128, 33, 3, True, 96, {"clip.1": 0.05, "clip.3": 0.05}, False),
+    ("wide", 64, 128, 16, False, 96, {"clip.1": 0.2, "clip.3": 0.2}, False),
+    ("wide", 64, 57, 11, True, 96, {"clip.1": 0.02, "clip.3": 0.02}, False),
 ]
 OFFPOLICY_T, OFFPOLICY_M, OFFPOLICY_RAGGED = 16, 4, 5
 

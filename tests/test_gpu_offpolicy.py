@@ -26,7 +26,10 @@ scale over the family's cases, every case printed by the test):
     family        noise scale s                                  overall  worst tensor
     sample-split  0.2 categorical; Gaussian 0.03, 0.05-0.08 (A=1)  2.1e-6   2.8e-6
     two-team      0.2 categorical; Gaussian 0.03                   1.6e-6   2.6e-6
-    wide          0.2 categorical; Gaussian 0.03, 0.1 (A=1)        3.4e-6   5.3e-6
+    wide          0.2 categorical; Gaussian 0.02-0.05, 0.1 (A=1)   3.4e-6   5.3e-6
+
+(the wide family's ten rows are one per reachable wide_mb_kernel<H, CONT, NB1>,
+tests/wide_mb_cases.py)
 
 Hand mutations of the three minibatch kernels (not committed): with `inr` replaced by 1.0f every
 item-1 case fails its overall bound (errors 6e-3 .. 0.7 of max|g|) while every gradient test that
