@@ -235,6 +235,10 @@ int validate_dims(const dppo_dims* d) {
               d->num_minibatches, d->world_size, d->rank);
     return DPPO_EINVAL;
   }
+  if (d->wide_ranks != 0 && d->wide_ranks != 1) {
+    set_error("invalid dims: wide_ranks must be 0 or 1 (got %d)", d->wide_ranks);
+    return DPPO_EINVAL;
+  }
   if ((int64_t)d->rollout_steps * d->num_envs > 0x7FFFFFFF) {
     set_error("T*N exceeds int32 sample indexing");
     return DPPO_EINVAL;
@@ -380,9 +384,10 @@ struct Timed {
 int require_mlp(const dppo_handle* h) {
   if (h->cls == kShapeNone) {
     set_error("fused MLP kernels support act_dim<=16 with hidden=64, obs_dim<=32 (tuned) or, on "
-              "one rank, hidden=128, obs_dim<=128 / hidden=64, 32<obs_dim<=128 (wide) "
-              "(got H=%d D=%d A=%d world=%d)",
-              h->dims.hidden, h->dims.obs_dim, h->dims.act_dim, h->dims.world_size);
+              "one rank or with wide_ranks, hidden=128, obs_dim<=128 / hidden=64, 32<obs_dim<=128 "
+              "(wide) (got H=%d D=%d A=%d world=%d wide_ranks=%d)",
+              h->dims.hidden, h->dims.obs_dim, h->dims.act_dim, h->dims.world_size,
+              h->dims.wide_ranks);
     return DPPO_EUNSUPPORTED;
   }
   return DPPO_OK;
@@ -918,11 +923,13 @@ int dppo_create(int device, const dppo_dims* dims, dppo_handle** out) {
   h->sh.R = D8 + 4 + (dims->continuous ? (dims->act_dim + 3) / 4 * 4 : 0);
   h->sh.H = dims->hidden;
   // tuned class (hidden 64, D <= 32): the minibatch kernels build a slab image in LDS; wide class
-  // (mbwide.hip): single rank only -- multi-rank wide learns stay with the caller's generic path
+  // (mbwide.hip): at world_size > 1 only where dims.wide_ranks asks for it -- otherwise multi-rank
+  // wide learns stay with the caller's generic path
   if (tuned_shape(h->sh)) {
     if (mb_lds_bytes(h->sh) <= 160 * 1024 && (size_t)(h->layout.total + 8) * 4 <= 160 * 1024)
       h->cls = kShapeTuned;
-  } else if (wide_shape(h->sh) && dims->world_size == 1 && wide_lds_bytes(h->sh) <= 160 * 1024) {
+  } else if (wide_shape(h->sh) && (dims->world_size == 1 || dims->wide_ranks) &&
+             wide_lds_bytes(h->sh) <= 160 * 1024) {
     h->cls = kShapeWide;
   }
   // One fused-minibatch workgroup per CU (its LDS footprint admits exactly one): never launch

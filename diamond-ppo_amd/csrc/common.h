@@ -311,6 +311,8 @@ int launch_mbw(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, in
 // Wide kernel family (mbwide.hip): hidden 128 with D <= 128, hidden 64 with 32 < D <= 128,
 // A <= 16.  One workgroup of H/16 waves per CU loops over 32-sample tiles and writes one slab;
 // wide_grid gives the workgroup count for a minibatch of m samples (at least two tiles each).
+// With a.seg (a rank's share of a global minibatch, sized on the device) G is the grid of a whole
+// global minibatch and workgroups past the share write zero slabs.
 size_t wide_lds_bytes(const MlpShape& sh);
 int wide_tile();
 int wide_grid(const MlpShape& sh, int32_t m);

@@ -84,6 +84,8 @@ struct WArgs {
   float* values;
   int64_t n;
   int D, D8, D16, A, R;
+  // minibatch kernel, SEG form (last: the fields above keep their kernel-argument offsets)
+  const int32_t* seg;  // global-minibatch DP: {start, end} of this minibatch in idx (device)
 };
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
@@ -338,8 +340,12 @@ __device__ __forceinline__ void policy_terms(const WArgs& a, const float* lds,
   }
 }
 
-// NB1: 16-column blocks of dW1 held in registers (>= D16 / 16: 2, 4 or 8)
-template <int H, bool CONT, int NB1>
+// NB1: 16-column blocks of dW1 held in registers (>= D16 / 16: 2, 4 or 8).  SEG: the minibatch is
+// idx[seg[0], seg[1]), a rank's share of a global minibatch.  A template parameter and not a
+// run-time branch: the H = 128 kernels are short of scalar registers, and the two values a branch
+// keeps live cost the categorical ones 4-16 B of scratch per lane; this way the !SEG kernels are
+// instruction for instruction what they were before segments existed.
+template <int H, bool CONT, int NB1, bool SEG>
 __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int SH = H + 4;
@@ -360,13 +366,23 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
 
   stage_heads<H>(a, lds, CONT);
   int* sidx = (int*)(lds + L.IDX);
-  const int ntiles = (a.m + S - 1) / S;
+  int mm = a.m;
+  const int32_t* idxp = a.idx;
+  if constexpr (SEG) {  // this rank's share of a global minibatch is known only on the device
+    const int s0 = a.seg[0];
+    mm = a.seg[1] - s0;
+    idxp += s0;
+  }
+  // A workgroup past the share's last tile (the grid is sized for a whole global minibatch; an
+  // empty share has no tile at all) skips the loop: its accumulators are still zero and the
+  // epilogue writes them, so its slab is a complete zero slab.
+  const int ntiles = (mm + S - 1) / S;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     // ---- gather: the samples' observation rows into X0 (zero past D and for samples past m)
     {
       const int i = tile * S + hs;
-      const bool valid = i < a.m;
-      const int id = valid ? a.idx[i] : -1;
+      const bool valid = i < mm;
+      const int id = valid ? idxp[i] : -1;
       if (li == 0) sidx[hs] = id;
       const f32x4* src = (const f32x4*)(a.rec + (int64_t)(valid ? id : 0) * a.R);
       for (int c = li; c < a.D16 / 4; c += LPS) {
@@ -727,12 +743,14 @@ WArgs base_args(const MlpShape& sh, const ParamOffsets& po, const float* params)
 
 void raise_wide_lds() {
   static const bool attr = [] {
-#define DPPO_WSET(H_, C_)                                     \
-  raise_dyn_lds((const void*)wide_mb_kernel<H_, C_, 2>);      \
-  raise_dyn_lds((const void*)wide_mb_kernel<H_, C_, 4>);      \
-  raise_dyn_lds((const void*)wide_mb_kernel<H_, C_, 8>);
+#define DPPO_WSET3(H_, C_, G_)                                  \
+  raise_dyn_lds((const void*)wide_mb_kernel<H_, C_, 2, G_>);    \
+  raise_dyn_lds((const void*)wide_mb_kernel<H_, C_, 4, G_>);    \
+  raise_dyn_lds((const void*)wide_mb_kernel<H_, C_, 8, G_>);
+#define DPPO_WSET(H_, C_) DPPO_WSET3(H_, C_, false) DPPO_WSET3(H_, C_, true)
     DPPO_WSET(64, false) DPPO_WSET(64, true) DPPO_WSET(128, false) DPPO_WSET(128, true)
 #undef DPPO_WSET
+#undef DPPO_WSET3
     raise_dyn_lds((const void*)wide_eval_kernel<64, false>);
     raise_dyn_lds((const void*)wide_eval_kernel<64, true>);
     raise_dyn_lds((const void*)wide_eval_kernel<128, false>);
@@ -765,13 +783,14 @@ int wide_grid(const MlpShape& sh, int32_t m) {
 
 int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& ga, int G,
                    hipStream_t s) {
-  if (!wide_shape(sh) || ga.seg) {
-    set_error("wide minibatch kernel: unsupported shape or global-minibatch segments");
+  if (!wide_shape(sh)) {
+    set_error("wide minibatch kernel: unsupported shape");
     return DPPO_EUNSUPPORTED;
   }
   WArgs k = base_args(sh, po, ga.params);
   k.rec = ga.rec;
   k.idx = ga.idx;
+  k.seg = ga.seg;  // with segments G is the handle's grid, sized for a whole global minibatch
   k.m = ga.m;
   k.inv_m = ga.inv_m;
   k.clip_eps = ga.clip_eps;
@@ -785,11 +804,16 @@ int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& g
   const dim3 grid((unsigned)(G < 1 ? 1 : G)), block((unsigned)(sh.H * 4));
   const bool c = sh.continuous != 0;
   const int nb1 = k.D16 / 16;
-#define DPPO_WLAUNCH(H_, C_)                                                                 \
+#define DPPO_WLAUNCH3(H_, C_, G_)                                                            \
   do {                                                                                       \
-    if (nb1 <= 2) DPPO_LAUNCH((wide_mb_kernel<H_, C_, 2>), grid, block, lds, s, k);          \
-    else if (nb1 <= 4) DPPO_LAUNCH((wide_mb_kernel<H_, C_, 4>), grid, block, lds, s, k);     \
-    else DPPO_LAUNCH((wide_mb_kernel<H_, C_, 8>), grid, block, lds, s, k);                   \
+    if (nb1 <= 2) DPPO_LAUNCH((wide_mb_kernel<H_, C_, 2, G_>), grid, block, lds, s, k);      \
+    else if (nb1 <= 4) DPPO_LAUNCH((wide_mb_kernel<H_, C_, 4, G_>), grid, block, lds, s, k); \
+    else DPPO_LAUNCH((wide_mb_kernel<H_, C_, 8, G_>), grid, block, lds, s, k);               \
+  } while (0)
+#define DPPO_WLAUNCH(H_, C_)                    \
+  do {                                          \
+    if (k.seg) DPPO_WLAUNCH3(H_, C_, true);     \
+    else DPPO_WLAUNCH3(H_, C_, false);          \
   } while (0)
   if (sh.H == 128) {
     if (c) DPPO_WLAUNCH(128, true);
@@ -799,6 +823,7 @@ int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& g
     else DPPO_WLAUNCH(64, false);
   }
 #undef DPPO_WLAUNCH
+#undef DPPO_WLAUNCH3
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }

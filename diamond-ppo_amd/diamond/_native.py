@@ -51,7 +51,9 @@ class Dims(ctypes.Structure):
                 ("continuous", ctypes.c_int32), ("hidden", ctypes.c_int32),
                 ("num_epochs", ctypes.c_int32), ("num_minibatches", ctypes.c_int32),
                 ("world_size", ctypes.c_int32), ("rank", ctypes.c_int32),
-                ("global_minibatches", ctypes.c_int32)]
+                ("global_minibatches", ctypes.c_int32),
+                # trailing, default 0: the wide class at world_size > 1 (dppo.h)
+                ("wide_ranks", ctypes.c_int32)]
 
 
 class HParams(ctypes.Structure):

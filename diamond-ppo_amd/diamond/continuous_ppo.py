@@ -63,6 +63,9 @@ class ContinuousPPOConfig:
     # chunked affine scan (chunk maps composed in parallel), within 1e-6 of the advantages' scale
     gae_bitexact: bool = True
     tanh_squash: bool = False  # extension: env actions tanh(u), experience keeps u (module doc)
+    # wide shape class on several ranks (additive, see PPOConfig.wide_data_parallel): False = the
+    # generic learn; True = the fused wide learn on every rank
+    wide_data_parallel: bool = False
 
 
 class JointNormal(torch.distributions.Normal):

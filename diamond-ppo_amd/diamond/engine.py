@@ -346,18 +346,20 @@ class _DraftWorker:
             del fn, done
 
 
-def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1):
+def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1,
+                      wide_ranks: bool = False):
     """Which fused kernel family serves the default network at this shape: ``"tuned"`` (hidden 64,
     obs_dim <= 32), ``"wide"`` (hidden 128 with obs_dim <= 128, or hidden 64 with
-    32 < obs_dim <= 128; one rank only) or ``None`` (the generic path).  The same predicate as
-    ``dppo_create`` (csrc/capi.cpp).  ``DPPO_WIDE=0`` turns the wide class off.  Both classes have
+    32 < obs_dim <= 128; at ``world > 1`` only with ``wide_ranks``, the configs'
+    ``wide_data_parallel`` / ``dppo_dims.wide_ranks``) or ``None`` (the generic path).  The same
+    predicate as ``dppo_create`` (csrc/capi.cpp).  ``DPPO_WIDE=0`` turns the wide class off.  Both classes have
     a fused learn and fused actor kernels; ``NativeLearner.act()`` uses the wide class's only when
     ``wide_act`` is set (its draws differ from ``network.get_actions``' torch stream)."""
     if not (1 <= act_dim <= 16 and obs_dim >= 1):
         return None
     if hidden == 64 and obs_dim <= 32:
         return "tuned"
-    if obs_dim <= 128 and (hidden == 128 or hidden == 64) and world == 1 \
+    if obs_dim <= 128 and (hidden == 128 or hidden == 64) and (world == 1 or wide_ranks) \
             and os.environ.get("DPPO_WIDE", "1") != "0":
         return "wide"
     return None
@@ -379,11 +381,14 @@ class NativeLearner:
         # global minibatches (cfg.global_minibatches, world > 1): the permutations span the
         # global batch of T * N * world samples and libdppo keeps this rank's members of each
         self.global_mb = bool(getattr(cfg, "global_minibatches", False)) and self.world > 1
+        # the wide class on several ranks is opt-in (cfg.wide_data_parallel; default: generic path)
+        self.wide_ranks = bool(getattr(cfg, "wide_data_parallel", False))
         self.dims = N.Dims(rollout_steps=self.T, num_envs=self.N, obs_dim=obs_dim,
                            act_dim=act_dim, continuous=int(continuous),
                            hidden=int(cfg.network_hidden_dim), num_epochs=cfg.num_epochs,
                            num_minibatches=cfg.num_minibatches, world_size=self.world,
-                           rank=self.rank, global_minibatches=int(self.global_mb))
+                           rank=self.rank, global_minibatches=int(self.global_mb),
+                           wide_ranks=int(self.wide_ranks))
         self.perm_n = self.T * self.N * (self.world if self.global_mb else 1)
         self.handle = N.Handle(device.index or 0, self.dims)
         if not getattr(cfg, "gae_bitexact", True):
@@ -394,7 +399,8 @@ class NativeLearner:
             tuple(p.shape) in ((L.rows[i], L.cols[i]), (L.rows[i],)) for i, (_, p) in
             enumerate(network.named_parameters()))
         self.shape_class = (fused_shape_class(int(cfg.network_hidden_dim), obs_dim, act_dim,
-                                              self.world) if shapes_ok else None)
+                                              self.world, self.wide_ranks)
+                            if shapes_ok else None)
         self.fused = self.shape_class is not None
         # act() serves the tuned class; the wide class only once wide_act is set (rollout() sets
         # it from the agent's fused_actions_wide): by default wide shapes sample their rollouts
@@ -511,15 +517,30 @@ class NativeLearner:
 
     def _init_peer(self, d, required: bool) -> bool:
         """Map every rank's exchange buffer and run one checked exchange; every rank keeps the
-        peer exchange only if every rank succeeded (ranks must never disagree on the transport)."""
+        peer exchange only if every rank succeeded (ranks must never disagree on the transport).
+        A parameter layout past the exchange's capacity (65,536 elements: wide H = 128 layouts
+        with many inputs) cannot export a buffer at all; the gathered tuples carry that too, so
+        every rank takes the same way out before any further collective."""
         h = self.handle
         # test hooks (DPPO_TEST_HOOKS=1, csrc/capi.cpp test_hook) must agree across ranks: a
         # sequence start that differs between ranks would stall every exchange
         hooks = ((os.environ.get("DPPO_PEER_XSEQ0"), os.environ.get("DPPO_PEER_SELFTEST_SKEW"))
                  if os.environ.get("DPPO_TEST_HOOKS") == "1" else None)
-        me = (h.peer_export(), self._gpu_identity(), hooks)
+        try:
+            blob, xerr = h.peer_export(), None
+        except (NotImplementedError, RuntimeError) as e:
+            blob, xerr = b"", str(e) or type(e).__name__
+        me = (blob, self._gpu_identity(), hooks, xerr)
         mine = [None] * self.world
         d.all_gather_object(mine, me)
+        bad = [(r, m[3]) for r, m in enumerate(mine) if m[3]]
+        if bad:   # the same list on every rank: the same message, and no rank maps anything
+            self.peer_status = f"export failed on rank {bad[0][0]}: {bad[0][1]}"
+            msg = f"peer exchange unavailable (rank {bad[0][0]}): {bad[0][1]}"
+            if required:
+                raise RuntimeError(msg)
+            warnings.warn(msg + "; RCCL carries the exchange")
+            return False
         gpus = [m[1] for m in mine]
         if len({m[2][0] if m[2] else None for m in mine}) > 1:
             err = "DPPO_PEER_XSEQ0 differs across ranks"

@@ -59,6 +59,11 @@ class PPOConfig:
     # GAE kernel (additive): True = the reference's serial recurrence, bit-exact; False = the
     # chunked affine scan (chunk maps composed in parallel), within 1e-6 of the advantages' scale
     gae_bitexact: bool = True
+    # wide shape class (hidden 128, or hidden 64 with 32 < obs_dim <= 128) on several ranks
+    # (additive): False = the generic torch-autograd learn, as before; True = the fused wide
+    # learn on every rank (local and global minibatches).  A layout past the peer exchange's
+    # 65,536 elements needs RCCL: DPPO_COMM=auto warns and keeps it, DPPO_COMM=peer raises
+    wide_data_parallel: bool = False
 
 
 class ActorCriticNetwork(nn.Module):
@@ -126,7 +131,10 @@ class _AgentBase:
     # or on an instance before rollout().  Measured on the stub env (profiles/wide_rollout.json,
     # T = 32, N = 32 / 1024 / 8192): a rollout is 5.5x / 3.0x / 1.48x faster at LunarLander-128
     # and 3.7x / 1.30x / 1.05x at Ant-64; the fused path lost at no measured shape or size, the
-    # last ratio is inside the run's spread
+    # last ratio is inside the run's spread.  On several ranks
+    # (cfg.wide_data_parallel) it does what the tuned sampler does: every rank draws from its own
+    # Philox key (_act_seed = f(cfg.seed) + rank) and its own call counter, so the ranks' env
+    # shards get independent action streams; it stays opt-in and off
     fused_actions_wide = False
 
     def _setup(self, env_fn, cfg, network_cls, envs=None):

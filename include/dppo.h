@@ -59,9 +59,10 @@ typedef struct dppo_dims {
   int32_t act_dim;         /* discrete: action_space.n; continuous: prod(action_space.shape) */
   int32_t continuous;      /* 0 = PPO/Categorical, 1 = ContinuousPPO/JointNormal */
   int32_t hidden;          /* network_hidden_dim (ppo.py:32,51).  Fused kernels, act_dim <= 16: the tuned
-                              class at 64 with obs_dim <= 32; the wide class (world_size 1) at 128
-                              with obs_dim <= 128 and at 64 with 32 < obs_dim <= 128.  Both serve the
-                              learn, evaluation and actor entry points */
+                              class at 64 with obs_dim <= 32; the wide class at 128 with obs_dim <= 128
+                              and at 64 with 32 < obs_dim <= 128 (world_size 1, or any world_size
+                              with wide_ranks below).  Both serve the learn, evaluation and actor
+                              entry points */
   int32_t num_epochs;      /* ppo.py:25 */
   int32_t num_minibatches; /* ppo.py:26 */
   int32_t world_size;      /* ranks sharing the env axis (1 = single GPU) */
@@ -75,6 +76,11 @@ typedef struct dppo_dims {
    *      the members of every global minibatch that fall in its env shard [rank*N, (rank+1)*N).
    *      world_size ranks then reproduce the single-GPU learn of the global batch. */
   int32_t global_minibatches;
+  /* 0 (default) = a wide shape at world_size > 1 gets no fused class (the caller's generic path);
+   * 1 = it gets the wide class: local and global minibatches, every communicator.  A layout past
+   * the peer exchange's 65,536 elements (dppo_peer_export: DPPO_EUNSUPPORTED) needs RCCL or a
+   * loopback group.  No effect at world_size 1 or on the tuned class. */
+  int32_t wide_ranks;
 } dppo_dims;
 
 /* Hyper-parameters of one learn() call (ppo.py:15-37, Adam defaults torch/optim/adam.py:39). */
