@@ -39,6 +39,7 @@ EXPORTED = [
     "dppo_gru_param_layout", "dppo_gru_create", "dppo_gru_destroy", "dppo_gru_minibatch_grad_f32",
     "dppo_gru_act_f32", "dppo_gru_value_f32", "dppo_gru_set_timing", "dppo_gru_get_timing",
     "dppo_gru_plan",
+    "dppo_ppo_loss_f32", "dppo_policy_logp_f32", "dppo_ppo_loss_plan",
 ]
 TIMING_CLASSES = ["eval", "gae", "adv_stats", "pack", "grad", "slab_reduce", "clip_adam",
                   "allreduce", "perm", "reduce_adam", "gae_probe"]
@@ -103,6 +104,24 @@ class LearnOutputs(ctypes.Structure):
     _fields_ = [("log_probs", ctypes.c_void_p), ("values", ctypes.c_void_p),
                 ("next_values", ctypes.c_void_p), ("advantages", ctypes.c_void_p),
                 ("returns", ctypes.c_void_p)]
+
+
+class LossArgs(ctypes.Structure):
+    """dppo_loss_args: one minibatch of the loss head (device pointers)."""
+    _fields_ = [("logits", ctypes.c_void_p), ("log_std", ctypes.c_void_p),
+                ("values", ctypes.c_void_p), ("idx", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("old_log_probs", ctypes.c_void_p),
+                ("advantages", ctypes.c_void_p), ("returns", ctypes.c_void_p),
+                ("d_logits", ctypes.c_void_p), ("d_log_std", ctypes.c_void_p),
+                ("d_values", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p),
+                ("m", ctypes.c_int64), ("rollout_len", ctypes.c_int64),
+                ("workspace_floats", ctypes.c_int64),
+                ("act_dim", ctypes.c_int32), ("continuous", ctypes.c_int32),
+                ("log_std_stride", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("ppo_clip", ctypes.c_double),
+                ("value_loss_weight", ctypes.c_float), ("entropy_beta", ctypes.c_float),
+                ("scale", ctypes.c_float), ("pad2_", ctypes.c_float)]
 
 
 _lib = None
@@ -185,6 +204,9 @@ def load():
         "dppo_gru_plan": (ctypes.c_int, [P(GruDims), vp]),
         "dppo_gru_set_timing": (ctypes.c_int, [vp, i32]),
         "dppo_gru_get_timing": (ctypes.c_int, [vp, vp, vp]),
+        "dppo_ppo_loss_f32": (ctypes.c_int, [P(LossArgs), vp]),
+        "dppo_policy_logp_f32": (ctypes.c_int, [vp, vp, i32, vp, vp, i64, i64, i32, i32, vp, vp]),
+        "dppo_ppo_loss_plan": (ctypes.c_int, [i64, i32, i32, P(i64), P(i32), P(i32)]),
         "dppo_set_timing": (ctypes.c_int, [vp, i32]),
         "dppo_get_timing": (ctypes.c_int, [vp, vp, vp]),
     }
@@ -229,6 +251,14 @@ def ptr(t) -> int:
     if isinstance(t, np.ndarray):
         return t.ctypes.data
     return t.data_ptr()
+
+
+def ppo_loss_plan(m: int, act_dim: int, continuous: bool = False):
+    """(workspace floats, workgroups, largest supported act_dim) of dppo_ppo_loss_f32."""
+    ws, grid, cap = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(load().dppo_ppo_loss_plan(int(m), int(act_dim), int(bool(continuous)), ctypes.byref(ws),
+                                    ctypes.byref(grid), ctypes.byref(cap)), "dppo_ppo_loss_plan")
+    return ws.value, grid.value, cap.value
 
 
 def param_layout(dims: Dims) -> Layout:

@@ -29,7 +29,9 @@ Two paths, chosen once per agent:
   ``DPPO_WIDE=0`` sends wide shapes down the generic path (A/B runs).
 * **generic** -- any other ``network_cls`` (reference readme.md:89-111): the network's own
   methods run forward/backward under torch autograd on the GPU; GAE, advantage statistics and
-  normalisation, and clip + Adam run in the HIP kernels (SURVEY.md §7.2 hard part 7).
+  normalisation, and clip + Adam run in the HIP kernels (SURVEY.md §7.2 hard part 7).  With the
+  agent's opt-in ``fused_loss`` the loss head between the network's outputs and ``backward()``
+  is HIP too (``fused_ppo_loss`` / ``policy_log_probs`` below, ``csrc/losshead.hip``).
 """
 from __future__ import annotations
 
@@ -365,6 +367,195 @@ def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1,
     return None
 
 
+def _torch_ppo_loss(logits, values, log_std, actions, old_log_probs, advantages, returns, idx,
+                    clip, value_loss_weight, entropy_beta, scale, continuous):
+    """The reference's minibatch loss as torch ops (ppo.py:264-280, continuous_ppo.py:276-292):
+    what ``fused_ppo_loss`` computes, and its fallback for inputs the kernel does not serve."""
+    if idx is not None:
+        actions, old_log_probs = actions[idx], old_log_probs[idx]
+        advantages, returns = advantages[idx], returns[idx]
+    if continuous:
+        from .continuous_ppo import JointNormal
+        dist = JointNormal(loc=logits, scale=log_std.exp())
+        new_lp = dist.log_prob(actions)
+    else:
+        dist = torch.distributions.Categorical(logits=logits)
+        new_lp = dist.log_prob(actions.long())
+    ratio = (new_lp - old_log_probs).exp()
+    l_pi = torch.max(-advantages * ratio,
+                     -advantages * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
+    l_v = 0.5 * torch.nn.functional.mse_loss(values, returns)
+    ent = dist.entropy().mean()
+    loss = l_pi + value_loss_weight * l_v + -entropy_beta * ent
+    if scale != 1.0:
+        loss = loss * scale
+    with torch.no_grad():
+        frac = ((ratio < 1.0 - clip) | (ratio > 1.0 + clip)).to(loss.dtype).mean()
+        parts = torch.stack([loss.detach(), l_pi.detach(), l_v.detach(), ent.detach(), frac])
+    return loss, parts
+
+
+def _torch_policy_log_probs(logits, log_std, actions, idx, continuous):
+    if idx is not None:
+        actions = actions[idx]
+    if continuous:
+        from .continuous_ppo import JointNormal
+        return JointNormal(loc=logits, scale=log_std.exp()).log_prob(actions)
+    return torch.distributions.Categorical(logits=logits).log_prob(actions.long())
+
+
+_LOSS_CAP = [None]
+LOSS_KERNEL_CALLS = [0]  # dppo_ppo_loss_f32 calls of this process (fallbacks do not count)
+
+
+def loss_head_max_actions() -> int:
+    """The widest logits row the loss-head kernels serve (``dppo_ppo_loss_plan``)."""
+    if _LOSS_CAP[0] is None:
+        _LOSS_CAP[0] = N.ppo_loss_plan(1, 1)[2]
+    return _LOSS_CAP[0]
+
+
+def _loss_head_serves(logits, values, log_std, actions, continuous) -> bool:
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2:
+        return False
+    m, A = logits.shape
+    if m == 0 or not 1 <= A <= loss_head_max_actions():
+        return False
+    if values is not None and (values.dtype != torch.float32 or values.numel() != m):
+        return False
+    if continuous:
+        return (log_std is not None and log_std.dtype == torch.float32
+                and actions.dtype == torch.float32 and log_std.shape[-1] == A)
+    return actions.dtype in (torch.int32, torch.int64)
+
+
+def _log_std_operand(log_std, m, A):
+    """(tensor, row stride) for the kernel: a broadcast row (every stride but the last is 0, as
+    ``broadcast_to`` of a [1, A] parameter returns) is passed as that one row."""
+    if log_std.dim() == 2 and log_std.shape[0] == m and log_std.stride(0) == 0 \
+            and (A == 1 or log_std.stride(1) == 1):
+        return log_std[0].contiguous(), 0
+    if log_std.numel() == A:
+        return log_std.reshape(A).contiguous(), 0
+    return log_std.expand(m, A).contiguous(), A
+
+
+def _loss_operands(actions, continuous):
+    """actions as the kernel reads them: int32 [B], or float32 [B][A], contiguous."""
+    if continuous:
+        return actions.contiguous()
+    return (actions if actions.dtype == torch.int32 else actions.to(torch.int32)).contiguous()
+
+
+class _FusedPPOLoss(torch.autograd.Function):
+    """dppo_ppo_loss_f32 as an autograd node: forward = the two launches on the current stream,
+    keeping the gradients with respect to the network's outputs; backward = those times
+    grad_output.  No host synchronisation in either."""
+
+    @staticmethod
+    def forward(ctx, logits, values, log_std, actions, old_log_probs, advantages, returns, idx,
+                clip, value_loss_weight, entropy_beta, scale, continuous):
+        m, A = logits.shape
+        dev = logits.device
+        lg = logits.detach().contiguous()
+        v = values.detach().reshape(m).contiguous()
+        ls, ls_stride = (None, 0)
+        if continuous:
+            ls, ls_stride = _log_std_operand(log_std.detach(), m, A)
+        d_logits = torch.empty_like(lg)
+        d_values = torch.empty_like(v)
+        d_log_std = torch.empty_like(lg) if continuous else None
+        out = torch.empty(8, dtype=torch.float32, device=dev)
+        ws_floats = N.ppo_loss_plan(m, A, continuous)[0]
+        ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+        if idx is not None:
+            idx = idx.to(torch.int64).contiguous()
+        args = N.LossArgs(
+            logits=lg.data_ptr(), log_std=ls.data_ptr() if continuous else None,
+            values=v.data_ptr(), idx=idx.data_ptr() if idx is not None else None,
+            actions=actions.data_ptr(), old_log_probs=old_log_probs.data_ptr(),
+            advantages=advantages.data_ptr(), returns=returns.data_ptr(),
+            d_logits=d_logits.data_ptr(),
+            d_log_std=d_log_std.data_ptr() if continuous else None,
+            d_values=d_values.data_ptr(), out=out.data_ptr(), workspace=ws.data_ptr(), m=m,
+            rollout_len=old_log_probs.numel(), workspace_floats=ws_floats, act_dim=A,
+            continuous=int(continuous), log_std_stride=ls_stride, ppo_clip=float(clip),
+            value_loss_weight=float(value_loss_weight), entropy_beta=float(entropy_beta),
+            scale=float(scale))
+        N.check(N.load().dppo_ppo_loss_f32(ctypes.byref(args),
+                                           torch.cuda.current_stream(dev).cuda_stream),
+                "dppo_ppo_loss_f32")
+        LOSS_KERNEL_CALLS[0] += 1
+        ctx.save_for_backward(d_logits, d_values, *([d_log_std] if continuous else []))
+        ctx.shapes = (values.shape, log_std.shape if continuous else None)
+        ctx.mark_non_differentiable(out)
+        # the loss as a tensor of its own: a view of `out` could not carry the graph
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_out):
+        saved = ctx.saved_tensors
+        v_shape, ls_shape = ctx.shapes
+        g_logits = saved[0] * g_loss
+        g_values = (saved[1] * g_loss).reshape(v_shape)
+        g_ls = None
+        if ls_shape is not None:
+            g_ls = saved[2] * g_loss
+            if tuple(ls_shape) != tuple(g_ls.shape):  # a [1, A] or [A] operand: sum the rows
+                g_ls = g_ls.sum(0).reshape(ls_shape)
+        return (g_logits, g_values, g_ls) + (None,) * 10
+
+
+def fused_ppo_loss(logits, values, log_std=None, *, actions, old_log_probs, advantages, returns,
+                   idx=None, clip, value_loss_weight, entropy_beta, scale=1.0, continuous=False):
+    """The PPO minibatch loss (reference ppo.py:264-280, continuous_ppo.py:276-292) and its
+    backward as one HIP kernel (csrc/losshead.hip) behind a ``torch.autograd.Function``.
+
+    ``logits`` [m, A] (categorical logits or Gaussian means) and ``values`` [m] are the network's
+    outputs for the minibatch and carry the autograd graph; ``log_std`` [m, A] (or a broadcast of
+    one row) likewise when ``continuous``.  ``actions`` (int32 / int64 [B], or float32 [B, A]),
+    ``old_log_probs``, ``advantages`` and ``returns`` (float32 [B]) are the rollout-flat arrays,
+    read through ``idx`` (int64 [m]; None = the first m entries in order).  Returns ``(loss,
+    parts)``: the scalar ``scale * (policy + value_loss_weight * value - entropy_beta * entropy)``
+    to call ``backward()`` on, and the detached device tensor ``{loss, policy, value, entropy,
+    clip fraction}``.  Inputs the kernel does not serve -- a dtype other than float32, more
+    actions than ``loss_head_max_actions()``, m == 0 -- take the torch expression instead."""
+    if not _loss_head_serves(logits, values, log_std, actions, continuous) \
+            or any(t.dtype != torch.float32 for t in (old_log_probs, advantages, returns)):
+        return _torch_ppo_loss(logits, values, log_std, actions, old_log_probs, advantages,
+                               returns, idx, clip, value_loss_weight, entropy_beta, scale,
+                               continuous)
+    loss, out = _FusedPPOLoss.apply(
+        logits, values, log_std, _loss_operands(actions, continuous), old_log_probs.contiguous(),
+        advantages.contiguous(), returns.contiguous(), idx, clip, value_loss_weight, entropy_beta,
+        scale, bool(continuous))
+    return loss, out[:5]
+
+
+def policy_log_probs(logits, log_std=None, *, actions, idx=None, continuous=False):
+    """log pi(actions | logits) without a graph: the forward-only twin of ``fused_ppo_loss`` (the
+    old-policy log-probs, ppo.py:235-237 / continuous_ppo.py:247-249), the same device function,
+    so an unchanged network gives ratio == 1 exactly.  Falls back as ``fused_ppo_loss`` does."""
+    if not _loss_head_serves(logits, None, log_std, actions, continuous):
+        return _torch_policy_log_probs(logits, log_std, actions, idx, continuous)
+    m, A = logits.shape
+    dev = logits.device
+    lg = logits.detach().contiguous()
+    ls, ls_stride = (None, 0)
+    if continuous:
+        ls, ls_stride = _log_std_operand(log_std.detach(), m, A)
+    acts = _loss_operands(actions, continuous)
+    if idx is not None:
+        idx = idx.to(torch.int64).contiguous()
+    logp = torch.empty(m, dtype=torch.float32, device=dev)
+    B = acts.shape[0]
+    N.check(N.load().dppo_policy_logp_f32(
+        lg.data_ptr(), ls.data_ptr() if continuous else None, ls_stride,
+        idx.data_ptr() if idx is not None else None, acts.data_ptr(), m, B, A, int(continuous),
+        logp.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dppo_policy_logp_f32")
+    return logp
+
+
 class NativeLearner:
     """Binds one agent (network + Adam) to a libdppo handle for its rollout shape."""
 
@@ -407,6 +598,10 @@ class NativeLearner:
         # with network.get_actions, as the reference does
         self.fused_act = self.shape_class == "tuned"
         self.wide_act = False
+        # the generic learn's loss head as HIP kernels (learn_device sets it from the agent's
+        # fused_loss); loss_head_calls counts the minibatches whose loss the kernel computed
+        self.fused_loss = False
+        self.loss_head_calls = 0
         if self.fused:
             self.flat = FlatParams(network, device, [L.offset[i] for i in range(L.count)], L.total)
         else:
@@ -872,15 +1067,26 @@ class NativeLearner:
         B = T * Nn
         stream = torch.cuda.current_stream(self.device).cuda_stream
         net = self.network
+        fused_loss = self.fused_loss
         with torch.inference_mode():
             if self.continuous:
                 means, log_stds, values = net.get_means_log_stds_and_values(ro.obs)
-                from .continuous_ppo import JointNormal
-                log_probs = JointNormal(loc=means, scale=log_stds.exp()).log_prob(ro.actions)
+                if fused_loss:
+                    A_ = means.shape[-1]
+                    log_probs = policy_log_probs(
+                        means.reshape(-1, A_), log_stds.reshape(-1, A_),
+                        actions=ro.actions.reshape(-1, A_), continuous=True)
+                else:
+                    from .continuous_ppo import JointNormal
+                    log_probs = JointNormal(loc=means, scale=log_stds.exp()).log_prob(ro.actions)
             else:
                 logits, values = net.get_logits_and_values(ro.obs)
-                log_probs = torch.distributions.Categorical(logits=logits).log_prob(
-                    ro.actions.long())
+                if fused_loss:
+                    log_probs = policy_log_probs(logits.reshape(-1, logits.shape[-1]),
+                                                 actions=ro.actions.reshape(-1))
+                else:
+                    log_probs = torch.distributions.Categorical(logits=logits).log_prob(
+                        ro.actions.long())
             next_values = net.get_values(ro.next_obs)
         values = values.float().contiguous()
         next_values = next_values.float().contiguous()
@@ -896,7 +1102,7 @@ class NativeLearner:
                     "dppo_adv_normalize_f32")
         obs = ro.obs.reshape(B, *ro.obs.shape[2:])
         acts = ro.actions.reshape(B, *ro.actions.shape[2:])
-        if not self.continuous:
+        if not self.continuous and not fused_loss:
             acts = acts.long()
         log_probs, adv, ret = log_probs.reshape(B), adv.reshape(B), ret.reshape(B)
         E, M = cfg.num_epochs, cfg.num_minibatches
@@ -932,24 +1138,38 @@ class NativeLearner:
                         self.v.data_ptr(), self.flat.total, cfg.grad_norm_clip, float(lr), 0.9,
                         0.999, cfg.adam_eps, step, None, stream), "dppo_clip_adam_f32")
                     continue
-                if self.continuous:
-                    from .continuous_ppo import JointNormal
-                    m_, ls_, v_ = net.get_means_log_stds_and_values(obs[mb_idx])
-                    dist = JointNormal(loc=m_, scale=ls_.exp())
-                    new_v = v_
+                if fused_loss:
+                    # the kernel reads acts / log_probs / adv / ret through mb_idx itself
+                    if self.continuous:
+                        hd, ls_, new_v = net.get_means_log_stds_and_values(obs[mb_idx])
+                    else:
+                        (hd, new_v), ls_ = net.get_logits_and_values(obs[mb_idx]), None
+                    calls0 = LOSS_KERNEL_CALLS[0]
+                    loss, _ = fused_ppo_loss(
+                        hd, new_v, ls_, actions=acts, old_log_probs=log_probs, advantages=adv,
+                        returns=ret, idx=mb_idx, clip=cfg.ppo_clip,
+                        value_loss_weight=cfg.value_loss_weight, entropy_beta=cfg.entropy_beta,
+                        scale=share if self.world > 1 else 1.0, continuous=self.continuous)
+                    self.loss_head_calls += LOSS_KERNEL_CALLS[0] - calls0
                 else:
-                    lg, new_v = net.get_logits_and_values(obs[mb_idx])
-                    dist = torch.distributions.Categorical(logits=lg)
-                new_lp = dist.log_prob(acts[mb_idx])
-                ratio = (new_lp - log_probs[mb_idx]).exp()
-                a_mb = adv[mb_idx]
-                l_pi = torch.max(-a_mb * ratio,
-                                 -a_mb * torch.clamp(ratio, 1.0 - cfg.ppo_clip, 1.0 + cfg.ppo_clip)).mean()
-                l_v = 0.5 * torch.nn.functional.mse_loss(new_v, ret[mb_idx])
-                ent = dist.entropy().mean()
-                loss = l_pi + cfg.value_loss_weight * l_v + -cfg.entropy_beta * ent
-                if self.world > 1:
-                    loss = loss * share
+                    if self.continuous:
+                        from .continuous_ppo import JointNormal
+                        m_, ls_, v_ = net.get_means_log_stds_and_values(obs[mb_idx])
+                        dist = JointNormal(loc=m_, scale=ls_.exp())
+                        new_v = v_
+                    else:
+                        lg, new_v = net.get_logits_and_values(obs[mb_idx])
+                        dist = torch.distributions.Categorical(logits=lg)
+                    new_lp = dist.log_prob(acts[mb_idx])
+                    ratio = (new_lp - log_probs[mb_idx]).exp()
+                    a_mb = adv[mb_idx]
+                    l_pi = torch.max(-a_mb * ratio, -a_mb * torch.clamp(
+                        ratio, 1.0 - cfg.ppo_clip, 1.0 + cfg.ppo_clip)).mean()
+                    l_v = 0.5 * torch.nn.functional.mse_loss(new_v, ret[mb_idx])
+                    ent = dist.entropy().mean()
+                    loss = l_pi + cfg.value_loss_weight * l_v + -cfg.entropy_beta * ent
+                    if self.world > 1:
+                        loss = loss * share
                 loss.backward()
                 if self.world > 1:
                     torch.distributed.all_reduce(self.flat.grad)

@@ -136,6 +136,12 @@ class _AgentBase:
     # Philox key (_act_seed = f(cfg.seed) + rank) and its own call counter, so the ranks' env
     # shards get independent action streams; it stays opt-in and off
     fused_actions_wide = False
+    # the generic learn (custom network_cls, shapes outside the fused classes) takes the
+    # old-policy log-probs and each minibatch's loss with its backward from the loss-head kernels
+    # (engine.policy_log_probs / fused_ppo_loss, csrc/losshead.hip) instead of the torch op
+    # chain; the network itself stays under autograd.  Off by default: the results agree with
+    # the torch chain to float32 rounding, not bit for bit.  No effect on a fused shape class
+    fused_loss = False
 
     def _setup(self, env_fn, cfg, network_cls, envs=None):
         self.device = require_gpu(getattr(cfg, "device_index", 0))
@@ -294,6 +300,7 @@ class _AgentBase:
 
     def learn_device(self, rollout: DeviceRollout, outputs: N.LearnOutputs | None = None) -> None:
         """learn() on a rollout already resident in HBM (the benchmarked hot path)."""
+        self._learner.fused_loss = bool(self.fused_loss)
         self._learner.learn(rollout, self.optimizer.param_groups[0]["lr"], outputs)
         self.lr_scheduler.step()                                        # ppo.py:287
 

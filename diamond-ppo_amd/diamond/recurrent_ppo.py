@@ -34,7 +34,7 @@ import torch.nn as nn
 from . import _native as N
 from ._spaces import is_box, is_discrete, make_vector_env
 from .engine import FlatParams, bind_adam_state, adam_step_count, advance_adam_steps, \
-    dist_world, require_gpu
+    dist_world, fused_ppo_loss, require_gpu, LOSS_KERNEL_CALLS
 from .utils import Checkpointer, Logger, Ticker, Timer
 
 
@@ -144,6 +144,10 @@ class RecurrentPPO:
     # conditions as fused_gru.  Off by default: the actions then come from torch's generator, as
     # before; the fused path draws from its own Philox stream (same distribution, other draws)
     fused_rollout = False
+    # the torch learn loop (custom network_cls or fused_gru = False) takes each minibatch's loss
+    # and its backward from the loss-head kernel (engine.fused_ppo_loss, csrc/losshead.hip)
+    # instead of the torch op chain; the network stays under autograd.  Off by default
+    fused_loss = False
 
     def __init__(self, env_fn: Callable[[], Any], cfg: RecurrentPPOConfig = RecurrentPPOConfig(),
                  network_cls: Any = RecurrentActorCriticNetwork, envs=None) -> None:
@@ -183,6 +187,7 @@ class RecurrentPPO:
                                                   enumerate(self.flat.offsets)):
                 raise RuntimeError("RecurrentActorCriticNetwork layout differs from libdppo's")
         self.last_losses = None
+        self.loss_head_calls = 0  # minibatches whose loss the loss-head kernel computed (fused_loss)
         # the fused rollout's Philox key (mixed as _AgentBase._act_seed) and call counter
         base_seed = cfg.seed if cfg.seed is not None else torch.initial_seed()
         self._act_seed = (int(base_seed) * 0x9E3779B97F4A7C15 + rank) & (2 ** 64 - 1)
@@ -362,21 +367,35 @@ class RecurrentPPO:
             advance_adam_steps(self.optimizer, self.flat, cfg.num_epochs * cfg.num_minibatches)
             self.lr_scheduler.step()
             return
+        fused_loss = bool(self.fused_loss)
+        if fused_loss:
+            act32 = actions.to(torch.int32).contiguous()
+            old_lp, adv_c, ret_c = (x.float().contiguous() for x in
+                                    (log_probs, advantages, returns))
         for b_idx in idx:
             for mb_idx in b_idx:
                 self.flat.grad.zero_()
                 nl, nv, _ = self.network.get_logits_values_and_hx(observations, hx, prev_dones)
                 nl, nv = flatten(nl)[mb_idx], flatten(nv)[mb_idx]
-                dist = torch.distributions.Categorical(logits=nl)
-                ratio = (dist.log_prob(actions[mb_idx]) - log_probs[mb_idx]).exp()
-                a = advantages[mb_idx]
-                l_pi = torch.max(-a * ratio, -a * torch.clamp(ratio, 1 - cfg.ppo_clip,
-                                                              1 + cfg.ppo_clip)).mean()
-                l_v = 0.5 * torch.nn.functional.mse_loss(nv, returns[mb_idx])
-                loss = l_pi + cfg.value_loss_weight * l_v - cfg.entropy_beta * dist.entropy().mean()
-                if world > 1:
-                    # local mean x 1/world, summed over the ranks = the union minibatch's mean
-                    loss = loss * (1.0 / world)
+                if fused_loss:
+                    calls0 = LOSS_KERNEL_CALLS[0]
+                    loss, _ = fused_ppo_loss(
+                        nl, nv, None, actions=act32, old_log_probs=old_lp, advantages=adv_c,
+                        returns=ret_c, idx=mb_idx, clip=cfg.ppo_clip,
+                        value_loss_weight=cfg.value_loss_weight, entropy_beta=cfg.entropy_beta,
+                        scale=1.0 / world if world > 1 else 1.0, continuous=False)
+                    self.loss_head_calls += LOSS_KERNEL_CALLS[0] - calls0
+                else:
+                    dist = torch.distributions.Categorical(logits=nl)
+                    ratio = (dist.log_prob(actions[mb_idx]) - log_probs[mb_idx]).exp()
+                    a = advantages[mb_idx]
+                    l_pi = torch.max(-a * ratio, -a * torch.clamp(ratio, 1 - cfg.ppo_clip,
+                                                                  1 + cfg.ppo_clip)).mean()
+                    l_v = 0.5 * torch.nn.functional.mse_loss(nv, returns[mb_idx])
+                    loss = l_pi + cfg.value_loss_weight * l_v - cfg.entropy_beta * dist.entropy().mean()
+                    if world > 1:
+                        # local mean x 1/world, summed over the ranks = the union minibatch's mean
+                        loss = loss * (1.0 / world)
                 loss.backward()
                 if world > 1:
                     torch.distributed.all_reduce(self.flat.grad)

@@ -520,6 +520,75 @@ int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs
 int dppo_gru_set_timing(dppo_gru_handle* h, int32_t enable);
 int dppo_gru_get_timing(dppo_gru_handle* h, double* ms_sum, int64_t* counts);
 
+/* ---- PPO loss head for a network that runs under the caller's autograd (custom network_cls,
+ * shapes outside the fused classes).  Handle-less, stream-ordered, allocates nothing, no host
+ * synchronisation, no floating-point atomics: the same inputs give the same bits. */
+
+/* One minibatch of m samples.  Device pointers unless stated. */
+typedef struct dppo_loss_args {
+  const float* logits;        /* [m][A] categorical logits or Gaussian means, dense */
+  const float* log_std;       /* continuous: [m][A] (log_std_stride == A) or one row [A]
+                                 (log_std_stride == 0); discrete: ignored, may be NULL */
+  const float* values;        /* [m] critic output */
+  const int64_t* idx;         /* [m] positions in the rollout-flat arrays below; NULL = 0..m-1.
+                                 An index outside [0, rollout_len) is never dereferenced: that
+                                 sample's outputs and the loss become NaN */
+  const void* actions;        /* int32 [rollout_len] or float32 [rollout_len][A] */
+  const float* old_log_probs; /* [rollout_len] */
+  const float* advantages;    /* [rollout_len] */
+  const float* returns;       /* [rollout_len] */
+  float* d_logits;            /* out [m][A]: d loss / d logits */
+  float* d_log_std;           /* out, continuous only: dense [m][A] (a broadcast row's gradient is
+                                 its column sum, as autograd's expand backward forms it) */
+  float* d_values;            /* out [m] */
+  float* out;                 /* out [8]: {loss, loss_policy, loss_value, entropy, clip fraction,
+                                 0, 0, 0}; loss = scale * (policy + value_loss_weight * value -
+                                 entropy_beta * entropy), the other terms are plain means over m;
+                                 clip fraction = share of samples with ratio strictly outside
+                                 [1 - ppo_clip, 1 + ppo_clip] */
+  float* workspace;           /* workspace_floats floats (dppo_ppo_loss_plan), 4-byte aligned */
+  int64_t m;
+  int64_t rollout_len;
+  int64_t workspace_floats;
+  int32_t act_dim;            /* A: 1 .. max_A of dppo_ppo_loss_plan (256) */
+  int32_t continuous;         /* 0 = Categorical, 1 = JointNormal */
+  int32_t log_std_stride;     /* 0 or A */
+  int32_t pad_;
+  double ppo_clip;            /* the config's Python float: the bounds are (float)(1.0 -+ clip),
+                                 what torch.clamp receives */
+  float value_loss_weight;
+  float entropy_beta;
+  float scale;                /* loss and gradients are multiplied by scale / m (1, or the share
+                                 a data-parallel rank multiplies its loss by) */
+  float pad2_;
+} dppo_loss_args;
+
+/* The minibatch loss and its gradient with respect to the network's outputs (replaces
+ * ppo.py:264-280 -- the gathers log_probs[mb], advantages[mb], returns[mb], actions[mb],
+ * Categorical(logits).log_prob / .entropy, ratio, clamp, max, mse_loss, the three means -- and
+ * continuous_ppo.py:276-292 with JointNormal (:39-47), plus autograd's backward of those ops at
+ * loss.backward(), ppo.py:283).  Backward conventions are torch's: maximum halves the gradient at
+ * a tie, clamp passes it on the closed interval.  Two launches.  DPPO_EINVAL, without a launch,
+ * for a NULL required pointer, m < 1, act_dim outside 1..max_A, log_std_stride other than 0 or
+ * act_dim, or workspace_floats below the plan's. */
+int dppo_ppo_loss_f32(const dppo_loss_args* args, void* stream);
+
+/* log pi(action | logits) for m samples, forward only (replaces the old-policy evaluation
+ * Categorical(logits).log_prob(actions), ppo.py:235-237, and JointNormal(...).log_prob,
+ * continuous_ppo.py:247-249): logp[m].  The same device function as dppo_ppo_loss_f32's forward,
+ * so equal inputs of equal alignment give the same bits and ratio == 1.  Arguments as the fields
+ * of dppo_loss_args; validation likewise. */
+int dppo_policy_logp_f32(const float* logits, const float* log_std, int32_t log_std_stride,
+                         const int64_t* idx, const void* actions, int64_t m, int64_t rollout_len,
+                         int32_t act_dim, int32_t continuous, float* logp, void* stream);
+
+/* Host only: the workspace (floats) dppo_ppo_loss_f32 needs for m samples of A, monotone in m;
+ * *grid = workgroups of the scalar-access form, each holding 256 / G samples per pass with
+ * G = min(64, the power of two >= A) lanes per row (a larger m takes further grid-stride passes);
+ * *max_A = the largest supported act_dim.  Any output may be NULL.  No reference counterpart. */
+int dppo_ppo_loss_plan(int64_t m, int32_t act_dim, int32_t continuous, int64_t* workspace_floats,
+                       int32_t* grid, int32_t* max_A);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
