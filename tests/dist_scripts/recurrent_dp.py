@@ -1,6 +1,9 @@
 """RecurrentPPO learn() in one rank of a world of `world` processes (gloo process group, every
 rank on cuda:0), for tests/test_gpu_recurrent.py.  Each rank learns on its slice of one synthetic
-rollout of the global env axis and writes its flat parameters.  Test infrastructure only."""
+rollout of the global env axis and writes its flat parameters.  With `torch_loop` the agent's
+fused_gru is switched off after construction and the rank runs two consecutive learns on two
+different rollouts through the torch loop, fused_loss off then on, for
+tests/test_gpu_generic_dp.py.  Test infrastructure only."""
 import os
 import sys
 
@@ -32,7 +35,7 @@ def shard(exp, lo, hi):
     return out
 
 
-def run(rank, world, port, T, Ng, D, A, out_path, gru_hidden_dim=16):
+def run(rank, world, port, T, Ng, D, A, out_path, gru_hidden_dim=16, torch_loop=False):
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     for p in (os.path.join(root, "diamond-ppo_amd"), os.path.join(root, "tests", "golden")):
         if p not in sys.path:
@@ -53,11 +56,29 @@ def run(rank, world, port, T, Ng, D, A, out_path, gru_hidden_dim=16):
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nl)
     agent = diamond.RecurrentPPO(None, cfg, envs=envs)
     assert agent.gru is not None, "gru_hidden_dim %d did not take the fused path" % gru_hidden_dim
-    exp = synth_experience(T, Ng, D, A, cfg.gru_hidden_dim, agent.device)
     init = agent.flat.flat.cpu().numpy()
-    agent.learn(shard(exp, rank * Nl, (rank + 1) * Nl))
-    torch.cuda.synchronize()
-    np.savez(out_path, init=init, final=agent.flat.flat.cpu().numpy())
+    if torch_loop:
+        res = {"init": init}
+        agent.fused_gru = False
+
+        def fused_learn_must_not_run(*a, **k):
+            raise AssertionError("fused_gru = False took the fused GRU kernel")
+
+        agent._learn_fused = fused_learn_must_not_run
+        for k, fused_loss in enumerate((False, True)):
+            agent.fused_loss = fused_loss
+            exp = synth_experience(T, Ng, D, A, cfg.gru_hidden_dim, agent.device, seed=k)
+            agent.learn(shard(exp, rank * Nl, (rank + 1) * Nl))
+            torch.cuda.synchronize()
+            assert agent.last_losses is None             # only the fused learn records them
+            res[f"final{k}"] = agent.flat.flat.cpu().numpy()
+            res[f"calls{k}"] = int(agent.loss_head_calls)
+        np.savez(out_path, **res)
+    else:
+        exp = synth_experience(T, Ng, D, A, cfg.gru_hidden_dim, agent.device)
+        agent.learn(shard(exp, rank * Nl, (rank + 1) * Nl))
+        torch.cuda.synchronize()
+        np.savez(out_path, init=init, final=agent.flat.flat.cpu().numpy())
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -208,6 +208,31 @@ def grad_bound(exact, f32):
     return max(4.0 * np.abs(f32 - exact).max(), 2e-5 * scale), scale
 
 
+DP_SCALES = [("1of3", 1 / 3), ("5of7", 5 / 7), ("1of8", 1 / 8)]
+DP_M_SIZES = [1, 2, 5, 65]
+# (m, k): one minibatch of m samples split into the shares [0, k) and [k, m) of two ranks
+PARTITIONS = [(7, 1), (7, 3), (65, 1), (65, 32)]
+# (Gaussian head, per-sample log_std rows): categorical, a broadcast log_std row, per-sample rows
+PARTITION_HEADS = [(False, False), (True, False), (True, True)]
+PARTITION_HEAD_IDS = ["cat", "gauss-broadcast", "gauss-rows"]
+
+
+def partition_case(m, cont, rows):
+    """The whole minibatch of a partition test (scale 1); `rows`: per-sample log_std rows."""
+    return make_case(m=m, A=3 if cont else 4, cont=cont, seed=60 + m, ls_stride=1 if rows else 0)
+
+
+def share(c, lo, hi):
+    """Samples [lo, hi) of minibatch c as the case one rank runs: the same rollout-flat arrays,
+    its rows of the network outputs, scale = its share of the minibatch."""
+    kw = dict(vars(c))
+    kw.update(m=hi - lo, scale=(hi - lo) / c.m, logits=c.logits[lo:hi], values=c.values[lo:hi],
+              idx=c.idx[lo:hi], gather=c.gather[lo:hi], third=c.third[lo:hi])
+    if c.cont and c.ls_stride:
+        kw["log_std"] = c.log_std[lo:hi]
+    return Case(**kw)
+
+
 def sweep_cases(cap):
     """The smallest cases at which each mechanism can go wrong: (label, kwargs of make_case)."""
     out = []
@@ -221,6 +246,12 @@ def sweep_cases(cap):
             out.append((f"m{m}", dict(m=m, A=4 if not cont else 3, cont=cont, seed=m)))
         out.append(("null-idx", dict(m=257, A=5, cont=cont, use_idx=False, seed=3)))
         out.append(("scale", dict(m=65, A=8, cont=cont, scale=0.125, seed=4)))
+        # the scale as data parallelism sets it: a rank's share k / mbp of a global minibatch
+        # (thirds, sevenths) or 1 / world, down to a single-sample share
+        for tag, sc in DP_SCALES:
+            for m in DP_M_SIZES:
+                out.append((f"scale{tag}-m{m}", dict(m=m, A=4 if not cont else 3, cont=cont,
+                                                      scale=sc, seed=50 + m)))
         for h in (1, 2):
             out.append((f"hyper{h}", dict(m=257, A=7, cont=cont, hyper=h, seed=5 + h)))
         out.append(("ret100", dict(m=257, A=4, cont=cont, regime="ret100", seed=8)))

@@ -149,6 +149,34 @@ def test_loss_and_gradients_match_float64(label, kw):
     check_case(label, C.make_case(**kw))
 
 
+@pytest.mark.parametrize("cont, rows", C.PARTITION_HEADS, ids=C.PARTITION_HEAD_IDS)
+@pytest.mark.parametrize("m, k", C.PARTITIONS)
+def test_shares_of_a_minibatch_reproduce_the_whole(m, k, cont, rows):
+    """`scale` as data parallelism uses it: two ranks run the kernel on their shares [0, k) and
+    [k, m) of one minibatch with scale = k / m and (m - k) / m.  The concatenated gradient rows
+    must be the float64 gradient of the whole minibatch at scale 1 within grad_bound, and the
+    shares' out[0] must add up to the whole loss within 2e-5 max(1, |loss|)."""
+    c = C.partition_case(m, cont, rows)
+    parts64, g64 = C.torch_loss(c, torch.float64)
+    _, g32 = C.torch_loss(c, torch.float32)
+    got = [run_loss(s) for s in (C.share(c, 0, k), C.share(c, k, m))]
+    loss = float(got[0][0][0]) + float(got[1][0][0])
+    print(f"m{m} k{k}: loss {loss} vs {parts64[0]}")
+    figures = {}
+    for key in g64:
+        cat = np.concatenate([g[key] for _, g in got]).astype(np.float64)
+        bound, scale = C.grad_bound(g64[key], g32[key])
+        figures[key] = (np.abs(cat - g64[key]).max() / scale, bound / scale)
+    print(f"m{m} k{k}: grad err/bound (of max|g|)", figures)
+    assert abs(loss - parts64[0]) <= 2e-5 * max(1.0, abs(parts64[0]))
+    for key, (err, bound) in figures.items():
+        assert err <= bound, (key, err, bound)
+    # the unscaled terms are each share's own means
+    for (out, _), s in zip(got, (C.share(c, 0, k), C.share(c, k, m))):
+        np.testing.assert_allclose(out[:5], C.torch_loss(s, torch.float64)[0], rtol=1e-5,
+                                   atol=1e-5)
+
+
 @pytest.mark.parametrize("cont", [False, True])
 def test_second_grid_stride_pass(cont):
     """An m the plan says one pass of the capped grid cannot hold."""

@@ -135,6 +135,31 @@ def test_case_meets_branch_condition_and_analytic_backward_is_autograd(label, kw
         assert np.abs(g_a[k] - g64[k]).max() <= 1e-12 * max(s, 1.0), (label, k)
 
 
+def test_sweep_covers_the_data_parallel_scales():
+    for cont in (False, True):
+        got = {(kw["scale"], kw["m"]) for _, kw in CASES if kw["cont"] == cont and "scale" in kw}
+        assert {(s, m) for _, s in C.DP_SCALES for m in C.DP_M_SIZES} <= got
+    assert [s for _, s in C.DP_SCALES] == [1 / 3, 5 / 7, 1 / 8] and C.DP_M_SIZES == [1, 2, 5, 65]
+
+
+@pytest.mark.parametrize("cont, rows", C.PARTITION_HEADS, ids=C.PARTITION_HEAD_IDS)
+@pytest.mark.parametrize("m, k", C.PARTITIONS)
+def test_shares_of_a_minibatch_sum_to_the_whole_in_float64(m, k, cont, rows):
+    """What the GPU partition test assumes: with scale = share / m the shares' gradient rows are
+    the whole minibatch's rows and their losses add up to its loss (float64 autograd)."""
+    torch = __import__("torch")
+    c = C.partition_case(m, cont, rows)
+    assert C.branch_margin(c) >= C.NEAR_BOUND and c.scale == 1.0
+    parts, g = C.torch_loss(c, torch.float64)
+    shares = [C.share(c, 0, k), C.share(c, k, m)]
+    assert [s.m for s in shares] == [k, m - k] and abs(sum(s.scale for s in shares) - 1) < 1e-15
+    got = [C.torch_loss(s, torch.float64) for s in shares]
+    assert abs(sum(p[0] for p, _ in got) - parts[0]) <= 1e-12 * max(1.0, abs(parts[0]))
+    for key in g:
+        cat = np.concatenate([gs[key] for _, gs in got])
+        assert np.abs(cat - g[key]).max() <= 1e-12 * max(1.0, np.abs(g[key]).max()), key
+
+
 def test_on_policy_case_has_unit_ratio_in_float64():
     c = C.make_case(m=65, A=5, cont=False, on_policy=True, seed=2)
     lp = C._logp64(c.logits, c.log_std, c.actions[c.gather], c.cont)

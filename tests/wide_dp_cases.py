@@ -198,11 +198,14 @@ def run_single(Hd, T, Ng, D, A, cont, M, flat0, host, perms_g):
 
 def oracle_learns(params, names, host, perms_list, cont, M):
     """The float32 oracle's consecutive learns of the global batch (params and Adam state carried
-    on); per learn (trace, copy of the parameters after it).  `params` is not modified."""
+    on); per learn (trace, copy of the parameters after it).  `params` is not modified.  `host`
+    is one rollout for every learn, or a list with one rollout per learn."""
     params = {n: params[n].copy() for n in names}
     adam = P.new_adam_state(params, names)
+    hosts = host if isinstance(host, list) else [host] * len(perms_list)
+    assert len(hosts) == len(perms_list)
     out = []
-    for perms_g in perms_list:
+    for host, perms_g in zip(hosts, perms_list):
         ref = P.learn(params, adam, list(host), P.Hyper(num_minibatches=M), 3e-4, cont,
                       perms=perms_g)
         out.append((ref, {n: params[n].copy() for n in names}))
