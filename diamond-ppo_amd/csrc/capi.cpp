@@ -385,7 +385,8 @@ int require_mlp(const dppo_handle* h) {
   if (h->cls == kShapeNone) {
     set_error("fused MLP kernels support act_dim<=16 with hidden=64, obs_dim<=32 (tuned) or, on "
               "one rank or with wide_ranks, hidden=128, obs_dim<=128 / hidden=64, 32<obs_dim<=128 "
-              "(wide) (got H=%d D=%d A=%d world=%d wide_ranks=%d)",
+              "(wide) or, on one rank, hidden=64, obs_dim<=384, act_dim<=32 (wide, large heads) "
+              "(got H=%d D=%d A=%d world=%d wide_ranks=%d)",
               h->dims.hidden, h->dims.obs_dim, h->dims.act_dim, h->dims.world_size,
               h->dims.wide_ranks);
     return DPPO_EUNSUPPORTED;
@@ -928,7 +929,8 @@ int dppo_create(int device, const dppo_dims* dims, dppo_handle** out) {
   if (tuned_shape(h->sh)) {
     if (mb_lds_bytes(h->sh) <= 160 * 1024 && (size_t)(h->layout.total + 8) * 4 <= 160 * 1024)
       h->cls = kShapeTuned;
-  } else if (wide_shape(h->sh) && (dims->world_size == 1 || dims->wide_ranks) &&
+  } else if (wide_shape(h->sh) &&
+             (dims->world_size == 1 || (dims->wide_ranks && !wide_large_shape(h->sh))) &&
              wide_lds_bytes(h->sh) <= 160 * 1024) {
     h->cls = kShapeWide;
   }

@@ -309,8 +309,8 @@ int launch_mbw(const MlpShape& sh, const ParamOffsets& po, const GradArgs& a, in
                hipStream_t s);
 
 // Wide kernel family (mbwide.hip): hidden 128 with D <= 128, hidden 64 with 32 < D <= 128,
-// A <= 16.  One workgroup of H/16 waves per CU loops over 32-sample tiles and writes one slab;
-// wide_grid gives the workgroup count for a minibatch of m samples (at least two tiles each).
+// A <= 16; hidden 64 also with D <= 384, A <= 32 where D > 128 or A > 16 (one rank).  One
+// workgroup of H/16 waves per CU loops over 32-sample tiles and writes one slab; wide_grid gives the workgroup count for a minibatch of m samples (at least two tiles each).
 // With a.seg (a rank's share of a global minibatch, sized on the device) G is the grid of a whole
 // global minibatch and workgroups past the share write zero slabs.
 size_t wide_lds_bytes(const MlpShape& sh);
@@ -335,7 +335,8 @@ int launch_wide_pack(const PackArgs& a, const float* mean_std, hipStream_t s);
 enum ShapeClass : int32_t { kShapeNone = 0, kShapeTuned = 1, kShapeWide = 2 };
 enum class MbKernel { None, Split /*mbwave.hip*/, Team /*mbstep.hip*/, Wide /*mbwide.hip*/ };
 bool tuned_shape(const MlpShape& sh);  // hidden 64, D <= 32, A <= 16
-bool wide_shape(const MlpShape& sh);
+bool wide_shape(const MlpShape& sh);        // includes wide_large_shape
+bool wide_large_shape(const MlpShape& sh);  // hidden 64, D <= 384, A <= 32, and D > 128 or A > 16
 MbKernel pick_mb_kernel(const MlpShape& sh, bool fused_tail);
 int fused_mb_grid(MbKernel k, const MlpShape& sh, int32_t m);
 int launch_fused_mb(MbKernel k, const MlpShape& sh, const ParamOffsets& po, const GradArgs& a,

@@ -2,15 +2,23 @@
 // sample-split kernel (mbwave.hip) where that kernel's own predicate admits the shape and the
 // two-team kernel (mbstep.hip) otherwise -- more actions, the fused Adam tail, DPPO_MB_LEGACY=1 --
 // with mlp.hip's evaluation and actor; the wide class (hidden 128, or hidden 64 with
-// 32 < D <= 128) has mbwide.hip for all three.  Host code only; the kernel files know nothing of
-// each other.
+// 32 < D <= 128; hidden 64 also "large heads", D <= 384 and A <= 32, on one rank) has mbwide.hip
+// for all three.  Host code only; the kernel files know nothing of each other.
 #include "common.h"
 
 namespace dppo {
 
 bool tuned_shape(const MlpShape& sh) { return sh.H == 64 && sh.D <= 32 && sh.A <= 16; }
 
+// Large heads: hidden 64 past either limit of the two classes above (Humanoid: 348 / 376 x 17).
+// The kernels have no segment form for it: one rank only (dppo_create).
+bool wide_large_shape(const MlpShape& sh) {
+  if (sh.H != 64 || sh.A < 1 || sh.A > 32 || sh.D < 1 || sh.D > 384) return false;
+  return sh.D > 128 || sh.A > 16;
+}
+
 bool wide_shape(const MlpShape& sh) {
+  if (wide_large_shape(sh)) return true;
   if (sh.A < 1 || sh.A > 16 || sh.D < 1 || sh.D > 128) return false;
   return sh.H == 128 || (sh.H == 64 && sh.D > 32);
 }

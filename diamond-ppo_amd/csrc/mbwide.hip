@@ -1,6 +1,8 @@
 // Wide kernel family: the fused PPO minibatch step, the old-policy evaluation and the rollout's
 // action sampling of the default actor-critic MLP at hidden 128 (1 <= D <= 128) and at hidden 64 with 33 <= D <= 128, where the
-// tuned kernels (mbwave.hip / mbstep.hip / mlp.hip: hidden 64, D <= 32) do not apply.
+// tuned kernels (mbwave.hip / mbstep.hip / mlp.hip: hidden 64, D <= 32) do not apply.  Hidden 64
+// goes on to "large heads" (dispatch.cpp wide_large_shape): D <= 384 and A <= 32, the second
+// block of 16 actions a compile-time choice (AB below) so that the A <= 16 kernels keep their code.
 //
 // Reference: loss and backward of one minibatch, diamond/ppo.py:261-283 (continuous:
 // continuous_ppo.py:273-295), default networks ppo.py:53-71 / continuous_ppo.py:63-81.
@@ -34,7 +36,9 @@ namespace dppo {
 namespace {
 
 constexpr int S = 32;     // samples per tile
-constexpr int SDO = 36;   // stride of the head-delta image: [0,16) dout, [16,32) d log_std terms
+// Head-delta image of AB blocks of 16 actions: per sample [0, 16 AB) dout, [16 AB, 32 AB) d log_std
+// terms, stride 32 AB + 4
+constexpr int sdo_of(int AB) { return 32 * AB + 4; }
 constexpr int kMinTiles = 2;  // tiles per workgroup before another workgroup (slab) is added
 constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
 constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;
@@ -45,7 +49,7 @@ struct WLds {  // offsets (floats)
   int total;
 };
 
-WLds make_wlds(int H, int D16) {
+WLds make_wlds(int H, int D16, int AB) {
   WLds L{};
   const int SH = H + 4;
   int o = 0;
@@ -56,11 +60,11 @@ WLds make_wlds(int H, int D16) {
   L.HA = o; o += S * SH;
   L.HC = o; o += S * SH;
   L.DZA = o; o += S * SH;
-  L.DOUT = o; o += S * SDO;
-  L.WO = o; o += 16 * H;
+  L.DOUT = o; o += S * sdo_of(AB);
+  L.WO = o; o += 16 * AB * H;
   L.WV = o; o += H;
-  L.BO = o; o += 16;
-  L.LS = o; o += 16;
+  L.BO = o; o += 16 * AB;
+  L.LS = o; o += 16 * AB;
   L.IDX = o; o += S;
   L.total = o;
   return L;
@@ -208,16 +212,16 @@ __device__ __forceinline__ float group_sum(float x, int r) {
   return (a + b) + (c + d);
 }
 
-// head weights into LDS: Wo rows >= A zero
-template <int H>
+// head weights into LDS: Wo rows >= A zero (NA = 16 AB rows)
+template <int H, int NA = 16>
 __device__ __forceinline__ void stage_heads(const WArgs& a, float* lds, bool cont) {
   constexpr int kThreads = H * 4;
   const int tid = threadIdx.x;
   const float* P = a.params;
-  for (int e = tid; e < 16 * H; e += kThreads)
+  for (int e = tid; e < NA * H; e += kThreads)
     lds[a.L.WO + e] = e < a.A * H ? P[a.po.Wo + e] : 0.0f;
   for (int e = tid; e < H; e += kThreads) lds[a.L.WV + e] = P[a.po.Wv + e];
-  if (tid < 16) {
+  if (tid < NA) {
     lds[a.L.BO + tid] = tid < a.A ? P[a.po.bo + tid] : 0.0f;
     lds[a.L.LS + tid] = cont && tid < a.A ? P[a.po.ls + tid] : 0.0f;
   }
@@ -255,14 +259,14 @@ __device__ __forceinline__ void forward_tile(const WArgs& a, float* lds, int q, 
   __syncthreads();
 }
 
-// Actor head of one sample on its H/8 lanes (8 hidden features each): out[16] (logits or Gaussian
+// Actor head of one sample on its H/8 lanes (8 hidden features each): out[NA] (logits or Gaussian
 // mean; entries >= A are bo's zero padding), identical in every lane of the sample.
-template <int H>
+template <int H, int NA>
 __device__ __forceinline__ void heads_actor(const WArgs& a, const float* lds, const float (&ha)[8],
-                                            int k0, bool actor, float (&out)[16]) {
+                                            int k0, bool actor, float (&out)[NA]) {
   constexpr int LPS = H / 8;
 #pragma unroll
-  for (int c = 0; c < 16; ++c) {
+  for (int c = 0; c < NA; ++c) {
     out[c] = 0.0f;
     if (actor && c < a.A) {
       const float* w = lds + a.L.WO + c * H + k0;
@@ -275,10 +279,10 @@ __device__ __forceinline__ void heads_actor(const WArgs& a, const float* lds, co
 }
 
 // Both heads of one sample: the value (identical in every lane of the sample), then heads_actor
-template <int H>
+template <int H, int NA>
 __device__ __forceinline__ void heads_fwd(const WArgs& a, const float* lds, const float (&ha)[8],
                                           const float (&hc)[8], int k0, bool actor,
-                                          float (&out)[16], float& v) {
+                                          float (&out)[NA], float& v) {
   constexpr int LPS = H / 8;
   float pv = 0.0f;
 #pragma unroll
@@ -289,16 +293,16 @@ __device__ __forceinline__ void heads_fwd(const WArgs& a, const float* lds, cons
 
 // log-probability and entropy of one sample; discrete: p[], lp[] of the softmax; continuous:
 // the per-action (x - mu) / var and z^2 - 1 left in p[], lp[]
-template <bool CONT>
+template <bool CONT, int NA>
 __device__ __forceinline__ void policy_terms(const WArgs& a, const float* lds,
-                                             const float (&out)[16], int action,
-                                             const float* __restrict__ xact, float (&p)[16],
-                                             float (&lp)[16], float& logp, float& ent) {
+                                             const float (&out)[NA], int action,
+                                             const float* __restrict__ xact, float (&p)[NA],
+                                             float (&lp)[NA], float& logp, float& ent) {
   if (CONT) {
     logp = 0.0f;
     ent = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) {
+    for (int c = 0; c < NA; ++c) {
       p[c] = 0.0f;
       lp[c] = 0.0f;
       if (c < a.A) {
@@ -317,17 +321,17 @@ __device__ __forceinline__ void policy_terms(const WArgs& a, const float* lds,
   } else {
     float mx = out[0];
 #pragma unroll
-    for (int c = 1; c < 16; ++c)
+    for (int c = 1; c < NA; ++c)
       if (c < a.A) mx = fmaxf(mx, out[c]);
     float se = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 16; ++c)
+    for (int c = 0; c < NA; ++c)
       if (c < a.A) se += expf(out[c] - mx);
     const float lse = mx + logf(se);
     logp = 0.0f;
     ent = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) {
+    for (int c = 0; c < NA; ++c) {
       p[c] = 0.0f;
       lp[c] = 0.0f;
       if (c < a.A) {
@@ -344,11 +348,14 @@ __device__ __forceinline__ void policy_terms(const WArgs& a, const float* lds,
 // idx[seg[0], seg[1]), a rank's share of a global minibatch.  A template parameter and not a
 // run-time branch: the H = 128 kernels are short of scalar registers, and the two values a branch
 // keeps live cost the categorical ones 4-16 B of scratch per lane; this way the !SEG kernels are
-// instruction for instruction what they were before segments existed.
-template <int H, bool CONT, int NB1, bool SEG>
+// instruction for instruction what they were before segments existed.  AB: blocks of 16 actions (1,
+// or 2 for 16 < A <= 32: twice the head registers, a second dWo accumulator); NA = 16 AB.
+template <int H, bool CONT, int NB1, bool SEG, int AB = 1>
 __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int SH = H + 4;
+  constexpr int NA = 16 * AB;
+  constexpr int SDO = sdo_of(AB);
   constexpr int NCB = H / 16;  // 16-column blocks of an H-wide matrix
   constexpr int LPS = H / 8;   // lanes per sample in the gather and head phases
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
@@ -359,12 +366,12 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
   const int ncb1 = a.D16 / 16;
 
   f32x4 aW1[NB1] = {}, aW2[NCB] = {}, aWa[NCB] = {}, aWc[NCB] = {};
-  f32x4 aWo = {};
-  float sb1 = 0.0f, sb2 = 0.0f, sba = 0.0f, sbc = 0.0f, sbo = 0.0f, sls = 0.0f;
+  f32x4 aWo[AB] = {};
+  float sb1 = 0.0f, sb2 = 0.0f, sba = 0.0f, sbc = 0.0f, sbo[AB] = {}, sls[AB] = {};
   float gWv[8] = {};
   float s_pi = 0.0f, s_v = 0.0f, s_h = 0.0f, s_bv = 0.0f;
 
-  stage_heads<H>(a, lds, CONT);
+  stage_heads<H, NA>(a, lds, CONT);
   int* sidx = (int*)(lds + L.IDX);
   int mm = a.m;
   const int32_t* idxp = a.idx;
@@ -403,11 +410,11 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
       *(f32x4*)&ha[4] = *(const f32x4*)(lds + L.HA + hs * SH + k0 + 4);
       *(f32x4*)&hc[0] = *(const f32x4*)(lds + L.HC + hs * SH + k0);
       *(f32x4*)&hc[4] = *(const f32x4*)(lds + L.HC + hs * SH + k0 + 4);
-      float out[16], v;
+      float out[NA], v;
       heads_fwd<H>(a, lds, ha, hc, k0, true, out, v);
       const float* sc = a.rec + (int64_t)(valid ? id : 0) * a.R + a.D8;
       const f32x4 s4 = *(const f32x4*)sc;  // {action bits, old log-prob, advantage, return}
-      float p[16], lp[16], logp, ent;
+      float p[NA], lp[NA], logp, ent;
       policy_terms<CONT>(a, lds, out, __float_as_int(s4[0]), sc + 4, p, lp, logp, ent);
       // clipped surrogate (ppo.py:266-270) and its derivative: maximum splits ties, clamp passes
       // the gradient on the closed interval
@@ -430,9 +437,9 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
         s_h += ent;
         s_bv += dv;
       }
-      float dout[16];
+      float dout[NA];
 #pragma unroll
-      for (int c = 0; c < 16; ++c) {
+      for (int c = 0; c < NA; ++c) {
         if (CONT) {
           dout[c] = dlogp * p[c];
           lp[c] = dlogp * lp[c];  // d log_std term
@@ -445,9 +452,9 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
       if (li == 0) {
         float* d = lds + L.DOUT + hs * SDO;
 #pragma unroll
-        for (int c = 0; c < 16; c += 4) {
+        for (int c = 0; c < NA; c += 4) {
           *(f32x4*)(d + c) = (f32x4){dout[c], dout[c + 1], dout[c + 2], dout[c + 3]};
-          *(f32x4*)(d + 16 + c) = (f32x4){lp[c], lp[c + 1], lp[c + 2], lp[c + 3]};
+          *(f32x4*)(d + NA + c) = (f32x4){lp[c], lp[c + 1], lp[c + 2], lp[c + 3]};
         }
       }
       float dza[8], dzc[8];
@@ -458,7 +465,7 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
         dzc[j] = dv * lds[L.WV + k0 + j] * (1.0f - hc[j] * hc[j]);
       }
 #pragma unroll
-      for (int c = 0; c < 16; ++c) {
+      for (int c = 0; c < NA; ++c) {
         if (c < a.A) {
           const float* wo = lds + L.WO + c * H + k0;
 #pragma unroll
@@ -484,10 +491,14 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
       const float* x = lds + L.HA + g * SH + 16 * q + r;
 #pragma unroll 2
       for (int t = 0; t < S / 4; ++t) {
-        const float av = z[4 * t * SDO];
-        sbo += av;
-        if (CONT) sls += z[4 * t * SDO + 16];
-        aWo = mfma4(av, x[4 * t * SH], aWo);
+        const float xv = x[4 * t * SH];
+#pragma unroll
+        for (int ab = 0; ab < AB; ++ab) {
+          const float av = z[4 * t * SDO + 16 * ab];
+          sbo[ab] += av;
+          if (CONT) sls[ab] += z[4 * t * SDO + NA + 16 * ab];
+          aWo[ab] = mfma4(av, xv, aWo[ab]);
+        }
       }
     }
     bwd_mm<H>(P + a.po.Wa, lds + L.DZA, q, lane, dh);
@@ -529,19 +540,33 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
     }
   }
 #pragma unroll
-  for (int v = 0; v < 4; ++v)
-    if (4 * g + v < a.A) slab[a.po.Wo + (4 * g + v) * H + 16 * q + r] = aWo[v];
+  for (int ab = 0; ab < AB; ++ab) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int c = 16 * ab + 4 * g + v;
+      if (c < a.A) slab[a.po.Wo + c * H + 16 * q + r] = aWo[ab][v];
+    }
+  }
   {
     const float t1 = group_sum(sb1, r), t2 = group_sum(sb2, r), ta = group_sum(sba, r),
-                tc = group_sum(sbc, r), to = group_sum(sbo, r), tl = group_sum(sls, r);
+                tc = group_sum(sbc, r);
+    float to[AB], tl[AB];
+#pragma unroll
+    for (int ab = 0; ab < AB; ++ab) {
+      to[ab] = group_sum(sbo[ab], r);
+      tl[ab] = group_sum(sls[ab], r);
+    }
     if (g == 0) {
       slab[a.po.b1 + 16 * q + r] = t1;
       slab[a.po.b2 + 16 * q + r] = t2;
       slab[a.po.ba + 16 * q + r] = ta;
       slab[a.po.bc + 16 * q + r] = tc;
-      if (q == 0 && r < a.A) {
-        slab[a.po.bo + r] = to;
-        if (CONT) slab[a.po.ls + r] = tl;
+#pragma unroll
+      for (int ab = 0; ab < AB; ++ab) {
+        if (q == 0 && 16 * ab + r < a.A) {
+          slab[a.po.bo + 16 * ab + r] = to[ab];
+          if (CONT) slab[a.po.ls + 16 * ab + r] = tl[ab];
+        }
       }
     }
   }
@@ -572,16 +597,17 @@ __global__ __launch_bounds__(H * 4, 1) void wide_mb_kernel(WArgs a) {
 }
 
 // Old-policy evaluation, one pass: log-probs (actions given) and values of obs[n][D]
-template <int H, bool CONT>
+template <int H, bool CONT, int AB = 1>
 __global__ __launch_bounds__(H * 4, 1) void wide_eval_kernel(WArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int SH = H + 4;
+  constexpr int NA = 16 * AB;
   constexpr int LPS = H / 8;
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
   const int hs = tid / LPS, li = tid % LPS, k0 = 8 * li;
   const WLds& L = a.L;
   const bool actor = a.actions != nullptr;
-  stage_heads<H>(a, lds, CONT);
+  stage_heads<H, NA>(a, lds, CONT);
   const int64_t ntiles = (a.n + S - 1) / S;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t i = tile * S + hs;
@@ -600,17 +626,17 @@ __global__ __launch_bounds__(H * 4, 1) void wide_eval_kernel(WArgs a) {
     }
     *(f32x4*)&hc[0] = *(const f32x4*)(lds + L.HC + hs * SH + k0);
     *(f32x4*)&hc[4] = *(const f32x4*)(lds + L.HC + hs * SH + k0 + 4);
-    float out[16], v;
+    float out[NA], v;
     heads_fwd<H>(a, lds, ha, hc, k0, actor, out, v);
     if (valid && li == 0) a.values[i] = v;
     if (actor) {
-      float p[16], lp[16], logp, ent;
-      float xa[16] = {};
+      float p[NA], lp[NA], logp, ent;
+      float xa[NA] = {};
       int action = 0;
       if (CONT) {
         const float* ac = (const float*)a.actions + (valid ? i : 0) * a.A;
 #pragma unroll
-        for (int c = 0; c < 16; ++c)
+        for (int c = 0; c < NA; ++c)
           if (c < a.A) xa[c] = ac[c];
       } else {
         action = ((const int32_t*)a.actions)[valid ? i : 0];
@@ -633,21 +659,22 @@ struct WActArgs {
   void* actions;
   float* env_act;
   int squash;  // 1: tanh(u), 2: sq_lo + (tanh(u) + 1) * sq_half
-  float sq_lo[16], sq_half[16], sq_hi[16];
+  float sq_lo[32], sq_half[32], sq_hi[32];
   uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
   int A;
 };
 
-template <int H, bool CONT>
+template <int H, bool CONT, int AB = 1>
 __global__ __launch_bounds__(H * 4, 1) void wide_act_kernel(WActArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int SH = H + 4;
+  constexpr int NA = 16 * AB;
   constexpr int LPS = H / 8;
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
   const int hs = tid / LPS, li = tid % LPS, k0 = 8 * li;
   const WArgs& w = a.w;
   const WLds& L = w.L;
-  stage_heads<H>(w, lds, CONT);
+  stage_heads<H, NA>(w, lds, CONT);
   const int64_t ntiles = (w.n + S - 1) / S;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t i = tile * S + hs;
@@ -662,19 +689,19 @@ __global__ __launch_bounds__(H * 4, 1) void wide_act_kernel(WActArgs a) {
     float ha[8];
     *(f32x4*)&ha[0] = *(const f32x4*)(lds + L.HA + hs * SH + k0);
     *(f32x4*)&ha[4] = *(const f32x4*)(lds + L.HA + hs * SH + k0 + 4);
-    float out[16];
+    float out[NA];
     heads_actor<H>(w, lds, ha, k0, true, out);
     if (valid && li == 0) {
       if (a.heads) {
 #pragma unroll
-        for (int c = 0; c < 16; ++c)
+        for (int c = 0; c < NA; ++c)
           if (c < a.A) a.heads[i * a.A + c] = out[c];
       }
       if (a.actions) {
         if (CONT) {
-          draw_gaussian<16>(a, out, lds + L.LS, i, (float*)a.actions + i * a.A);
+          draw_gaussian<NA>(a, out, lds + L.LS, i, (float*)a.actions + i * a.A);
         } else {
-          ((int32_t*)a.actions)[i] = draw_categorical<16>(a, out, i);
+          ((int32_t*)a.actions)[i] = draw_categorical<NA>(a, out, i);
         }
       }
     }
@@ -727,10 +754,12 @@ __global__ __launch_bounds__(256) void wide_pack_kernel(WPackArgs w) {
 
 inline int cus_of(const MlpShape& sh) { return sh.cus > 0 ? sh.cus : 256; }
 
+inline int ab_of(const MlpShape& sh) { return sh.A > 16 ? 2 : 1; }  // blocks of 16 actions
+
 WArgs base_args(const MlpShape& sh, const ParamOffsets& po, const float* params) {
   WArgs k{};
   const int D16 = (sh.D + 15) / 16 * 16;
-  k.L = make_wlds(sh.H, D16);
+  k.L = make_wlds(sh.H, D16, ab_of(sh));
   k.po = po;
   k.params = params;
   k.D = sh.D;
@@ -751,6 +780,21 @@ void raise_wide_lds() {
     DPPO_WSET(64, false) DPPO_WSET(64, true) DPPO_WSET(128, false) DPPO_WSET(128, true)
 #undef DPPO_WSET
 #undef DPPO_WSET3
+    // large heads: hidden 64, no segments; one action block only where D16 > 128
+#define DPPO_WSETL(C_)                                                \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 2, false, 2>);    \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 4, false, 2>);    \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 8, false, 2>);    \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 12, false, 1>);   \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 12, false, 2>);   \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 16, false, 1>);   \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 16, false, 2>);   \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 24, false, 1>);   \
+  raise_dyn_lds((const void*)wide_mb_kernel<64, C_, 24, false, 2>);   \
+  raise_dyn_lds((const void*)wide_eval_kernel<64, C_, 2>);            \
+  raise_dyn_lds((const void*)wide_act_kernel<64, C_, 2>);
+    DPPO_WSETL(false) DPPO_WSETL(true)
+#undef DPPO_WSETL
     raise_dyn_lds((const void*)wide_eval_kernel<64, false>);
     raise_dyn_lds((const void*)wide_eval_kernel<64, true>);
     raise_dyn_lds((const void*)wide_eval_kernel<128, false>);
@@ -767,7 +811,7 @@ void raise_wide_lds() {
 }  // namespace
 
 size_t wide_lds_bytes(const MlpShape& sh) {
-  return (size_t)make_wlds(sh.H, (sh.D + 15) / 16 * 16).total * sizeof(float);
+  return (size_t)make_wlds(sh.H, (sh.D + 15) / 16 * 16, ab_of(sh)).total * sizeof(float);
 }
 
 int wide_tile() { return S; }
@@ -785,6 +829,10 @@ int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& g
                    hipStream_t s) {
   if (!wide_shape(sh)) {
     set_error("wide minibatch kernel: unsupported shape");
+    return DPPO_EUNSUPPORTED;
+  }
+  if (wide_large_shape(sh) && ga.seg) {
+    set_error("wide minibatch kernel: large heads (obs_dim > 128 or act_dim > 16) run on one rank");
     return DPPO_EUNSUPPORTED;
   }
   WArgs k = base_args(sh, po, ga.params);
@@ -815,13 +863,36 @@ int launch_wide_mb(const MlpShape& sh, const ParamOffsets& po, const GradArgs& g
     if (k.seg) DPPO_WLAUNCH3(H_, C_, true);     \
     else DPPO_WLAUNCH3(H_, C_, false);          \
   } while (0)
-  if (sh.H == 128) {
+  // large heads (hidden 64, no segments): NB1 12 / 16 / 24 past D16 = 128, AB_ blocks of 16 actions
+#define DPPO_WLAUNCHL(C_, AB_)                                                                   \
+  do {                                                                                           \
+    if (nb1 <= 2) DPPO_LAUNCH((wide_mb_kernel<64, C_, 2, false, AB_>), grid, block, lds, s, k);  \
+    else if (nb1 <= 4)                                                                           \
+      DPPO_LAUNCH((wide_mb_kernel<64, C_, 4, false, AB_>), grid, block, lds, s, k);              \
+    else if (nb1 <= 8)                                                                           \
+      DPPO_LAUNCH((wide_mb_kernel<64, C_, 8, false, AB_>), grid, block, lds, s, k);              \
+    else if (nb1 <= 12)                                                                          \
+      DPPO_LAUNCH((wide_mb_kernel<64, C_, 12, false, AB_>), grid, block, lds, s, k);             \
+    else if (nb1 <= 16)                                                                          \
+      DPPO_LAUNCH((wide_mb_kernel<64, C_, 16, false, AB_>), grid, block, lds, s, k);             \
+    else DPPO_LAUNCH((wide_mb_kernel<64, C_, 24, false, AB_>), grid, block, lds, s, k);          \
+  } while (0)
+  if (wide_large_shape(sh)) {
+    if (sh.A > 16) {
+      if (c) DPPO_WLAUNCHL(true, 2);
+      else DPPO_WLAUNCHL(false, 2);
+    } else {
+      if (c) DPPO_WLAUNCHL(true, 1);
+      else DPPO_WLAUNCHL(false, 1);
+    }
+  } else if (sh.H == 128) {
     if (c) DPPO_WLAUNCH(128, true);
     else DPPO_WLAUNCH(128, false);
   } else {
     if (c) DPPO_WLAUNCH(64, true);
     else DPPO_WLAUNCH(64, false);
   }
+#undef DPPO_WLAUNCHL
 #undef DPPO_WLAUNCH
 #undef DPPO_WLAUNCH3
   DPPO_LAUNCH_CHECK();
@@ -849,7 +920,10 @@ int launch_wide_eval(const MlpShape& sh, const ParamOffsets& po, const float* pa
     k.values = pass == 0 ? values : next_values;
     k.n = n;
     const size_t lds = (size_t)k.L.total * sizeof(float);
-    if (sh.H == 128) {
+    if (sh.A > 16) {  // hidden 64: wide_shape
+      if (c) DPPO_LAUNCH((wide_eval_kernel<64, true, 2>), grid, block, lds, s, k);
+      else DPPO_LAUNCH((wide_eval_kernel<64, false, 2>), grid, block, lds, s, k);
+    } else if (sh.H == 128) {
       if (c) DPPO_LAUNCH((wide_eval_kernel<128, true>), grid, block, lds, s, k);
       else DPPO_LAUNCH((wide_eval_kernel<128, false>), grid, block, lds, s, k);
     } else {
@@ -871,8 +945,8 @@ int launch_wide_act(const MlpShape& sh, const ParamOffsets& po, const float* par
   if (n <= 0) return DPPO_OK;
   WActArgs k{};
   if (squash && squash->env_actions) {
-    if (!sh.continuous || sh.A > 16) {
-      set_error("tanh squash needs a continuous action space of at most 16 dims");
+    if (!sh.continuous || sh.A > 32) {
+      set_error("tanh squash needs a continuous action space of at most 32 dims");
       return DPPO_EINVAL;
     }
     k.env_act = squash->env_actions;
@@ -899,7 +973,10 @@ int launch_wide_act(const MlpShape& sh, const ParamOffsets& po, const float* par
   const int cus = cus_of(sh);
   const dim3 grid((unsigned)(ntiles < cus ? ntiles : cus)), block((unsigned)(sh.H * 4));
   const size_t lds = (size_t)k.w.L.total * sizeof(float);
-  if (sh.H == 128) {
+  if (sh.A > 16) {  // hidden 64: wide_shape
+    if (c) DPPO_LAUNCH((wide_act_kernel<64, true, 2>), grid, block, lds, s, k);
+    else DPPO_LAUNCH((wide_act_kernel<64, false, 2>), grid, block, lds, s, k);
+  } else if (sh.H == 128) {
     if (c) DPPO_LAUNCH((wide_act_kernel<128, true>), grid, block, lds, s, k);
     else DPPO_LAUNCH((wide_act_kernel<128, false>), grid, block, lds, s, k);
   } else {

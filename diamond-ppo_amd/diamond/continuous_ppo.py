@@ -64,7 +64,8 @@ class ContinuousPPOConfig:
     gae_bitexact: bool = True
     tanh_squash: bool = False  # extension: env actions tanh(u), experience keeps u (module doc)
     # wide shape class on several ranks (additive, see PPOConfig.wide_data_parallel): False = the
-    # generic learn; True = the fused wide learn on every rank
+    # generic learn; True = the fused wide learn on every rank (not the large heads, e.g.
+    # Humanoid's 376 x 17 at hidden 64: those are fused on one rank only)
     wide_data_parallel: bool = False
 
 

@@ -19,10 +19,12 @@ Two paths, chosen once per agent:
 
 * **fused** -- default network at supported sizes: everything in ``dppo_learn_f32`` (old-policy
   eval, GAE, normalisation, E x M fused minibatch steps with clip + Adam, RCCL all-reduces when
-  sharded).  Two shape classes (``fused_shape_class``), actions <= 16 in both:
-  **tuned** -- hidden 64, obs_dim <= 32: the register-resident kernels, and ``act()`` samples the
-  rollout's actions in HIP too;
-  **wide** -- hidden 128 with obs_dim <= 128, or hidden 64 with 32 < obs_dim <= 128, one rank
+  sharded).  Two shape classes (``fused_shape_class``):
+  **tuned** -- hidden 64, obs_dim <= 32, actions <= 16: the register-resident kernels, and
+  ``act()`` samples the rollout's actions in HIP too;
+  **wide** -- hidden 128 with obs_dim <= 128, or hidden 64 with 32 < obs_dim <= 128, actions
+  <= 16, one rank; and at hidden 64 on one rank the "large heads" past either limit, obs_dim <= 384
+  and actions <= 32 (Humanoid: 348 / 376 x 17)
   (``csrc/mbwide.hip``): the same learn, while rollouts sample with ``network.get_actions`` as
   the reference does unless the agent opts in (``fused_actions_wide`` -> ``wide_act``): then
   ``act()`` runs ``wide_act_kernel`` and draws the tuned class's Philox stream.
@@ -351,18 +353,25 @@ class _DraftWorker:
 def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1,
                       wide_ranks: bool = False):
     """Which fused kernel family serves the default network at this shape: ``"tuned"`` (hidden 64,
-    obs_dim <= 32), ``"wide"`` (hidden 128 with obs_dim <= 128, or hidden 64 with
-    32 < obs_dim <= 128; at ``world > 1`` only with ``wide_ranks``, the configs'
-    ``wide_data_parallel`` / ``dppo_dims.wide_ranks``) or ``None`` (the generic path).  The same
+    obs_dim <= 32, act_dim <= 16), ``"wide"`` (act_dim <= 16 and hidden 128 with obs_dim <= 128 or
+    hidden 64 with 32 < obs_dim <= 128; at ``world > 1`` only with ``wide_ranks``, the configs'
+    ``wide_data_parallel`` / ``dppo_dims.wide_ranks``; and the large heads: hidden 64 with
+    obs_dim <= 384 and act_dim <= 32 where obs_dim > 128 or act_dim > 16, at ``world == 1``
+    only, whatever ``wide_ranks`` says) or ``None`` (the generic path).  The same
     predicate as ``dppo_create`` (csrc/capi.cpp).  ``DPPO_WIDE=0`` turns the wide class off.  Both classes have
     a fused learn and fused actor kernels; ``NativeLearner.act()`` uses the wide class's only when
     ``wide_act`` is set (its draws differ from ``network.get_actions``' torch stream)."""
-    if not (1 <= act_dim <= 16 and obs_dim >= 1):
+    if act_dim < 1 or obs_dim < 1:
+        return None
+    wide_on = os.environ.get("DPPO_WIDE", "1") != "0"
+    if hidden == 64 and obs_dim <= 384 and act_dim <= 32 and (obs_dim > 128 or act_dim > 16):
+        return "wide" if world == 1 and wide_on else None  # large heads
+    if act_dim > 16:
         return None
     if hidden == 64 and obs_dim <= 32:
         return "tuned"
     if obs_dim <= 128 and (hidden == 128 or hidden == 64) and (world == 1 or wide_ranks) \
-            and os.environ.get("DPPO_WIDE", "1") != "0":
+            and wide_on:
         return "wide"
     return None
 

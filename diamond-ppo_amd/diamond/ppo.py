@@ -62,7 +62,9 @@ class PPOConfig:
     # wide shape class (hidden 128, or hidden 64 with 32 < obs_dim <= 128) on several ranks
     # (additive): False = the generic torch-autograd learn, as before; True = the fused wide
     # learn on every rank (local and global minibatches).  A layout past the peer exchange's
-    # 65,536 elements needs RCCL: DPPO_COMM=auto warns and keeps it, DPPO_COMM=peer raises
+    # 65,536 elements needs RCCL: DPPO_COMM=auto warns and keeps it, DPPO_COMM=peer raises.  The
+    # wide class's large heads (hidden 64 with obs_dim > 128 or more than 16 actions, up to 384
+    # and 32) are fused on one rank only: several ranks keep the generic learn, flag or not
     wide_data_parallel: bool = False
 
 
@@ -126,7 +128,8 @@ class _AgentBase:
     # (dppo_act_f32: same distribution as get_actions, Philox draws instead of torch's); False, or
     # any other network_cls, calls network.get_actions as the reference does
     fused_actions = True
-    # the same for the wide shape class (hidden 128, or hidden 64 with 32 < obs_dim <= 128), off
+    # the same for the wide shape class (hidden 128, or hidden 64 with 32 < obs_dim <= 128; at
+    # hidden 64 also its large heads, obs_dim <= 384 and up to 32 actions), off
     # by default because it replaces torch's action stream with the Philox one; set on the class
     # or on an instance before rollout().  Measured on the stub env (profiles/wide_rollout.json,
     # T = 32, N = 32 / 1024 / 8192): a rollout is 5.5x / 3.0x / 1.48x faster at LunarLander-128

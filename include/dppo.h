@@ -61,7 +61,10 @@ typedef struct dppo_dims {
   int32_t hidden;          /* network_hidden_dim (ppo.py:32,51).  Fused kernels, act_dim <= 16: the tuned
                               class at 64 with obs_dim <= 32; the wide class at 128 with obs_dim <= 128
                               and at 64 with 32 < obs_dim <= 128 (world_size 1, or any world_size
-                              with wide_ranks below).  Both serve the learn, evaluation and actor
+                              with wide_ranks below).  The wide class also takes, at hidden 64 and
+                              world_size 1 only (wide_ranks or not), the large heads: obs_dim <= 384
+                              and act_dim <= 32 with obs_dim > 128 or act_dim > 16 (Humanoid:
+                              348 / 376 x 17).  Both serve the learn, evaluation and actor
                               entry points */
   int32_t num_epochs;      /* ppo.py:25 */
   int32_t num_minibatches; /* ppo.py:26 */
@@ -77,7 +80,8 @@ typedef struct dppo_dims {
    *      world_size ranks then reproduce the single-GPU learn of the global batch. */
   int32_t global_minibatches;
   /* 0 (default) = a wide shape at world_size > 1 gets no fused class (the caller's generic path);
-   * 1 = it gets the wide class: local and global minibatches, every communicator.  A layout past
+   * 1 = it gets the wide class (but for the large heads, see `hidden`: those stay without a
+   * fused class at world_size > 1): local and global minibatches, every communicator.  A layout past
    * the peer exchange's 65,536 elements (dppo_peer_export: DPPO_EUNSUPPORTED) needs RCCL or a
    * loopback group.  No effect at world_size 1 or on the tuned class. */
   int32_t wide_ranks;

@@ -12,7 +12,8 @@ a difference counts only where the two min-max ranges do not overlap.
 
 Every shape takes the generic path: a subclass of the default discrete network (the plug-in
 interface), the default network at a hidden width outside the fused classes, and a
-Humanoid-sized Gaussian policy (348 inputs, 17 actions).
+Humanoid-sized Gaussian policy (348 inputs, 17 actions) -- a subclass as well, since the default
+network at that shape runs the wide family's fused learn.
 
 Also recorded, with device events over back-to-back calls on minibatch-sized inputs: the stream
 time per dppo_ppo_loss_f32 call (its two launches) and per dppo_policy_logp_f32 launch over the
@@ -46,7 +47,7 @@ T = 128
 SHAPES = [
     ("custom-net D8 A4 H64 N8192", 8192, 8, 4, False, 64, True),
     ("default-net H256 D8 A4 N8192", 8192, 8, 4, False, 256, False),
-    ("Humanoid-shaped D348 A17 H64 N4096", 4096, 348, 17, True, 64, False),
+    ("Humanoid-shaped D348 A17 H64 N4096", 4096, 348, 17, True, 64, True),
 ]
 
 

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Time learn_device() on a resident rollout at three shapes outside the tuned class.
+"""Time learn_device() on a resident rollout at shapes outside the tuned class.
 
     python tools/bench_wide.py --out profiles/wide_learn.json
+    python tools/bench_wide.py --only Humanoid-348 --only Humanoid-376 --compare-generic \
+        --out profiles/wide_learn_large.json
 
 At a commit with the wide kernel family (csrc/mbwide.hip) these shapes run the fused HIP learn; at
 an earlier commit -- or with DPPO_WIDE=0 -- they take the generic path (network under torch
@@ -14,11 +16,16 @@ is reported with min and max.  With the fused path it also reads the library's p
 timing for one learn and derives the minibatch kernel's time per launch and its fraction of the
 157.3 TF fp32 MFMA peak in SURVEY §8(d)'s unit: 2 (3F - D H) FLOP per sample,
 F = D H + 3 H^2 + H (A + 1).
+
+`--compare-generic` adds, per shape, the generic path as a child process with DPPO_WIDE=0 runs it
+(the same script and tree, `--fused-loss` off and on), and whether the fused learn's slowest run is
+below the generic path's fastest.
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -37,6 +44,9 @@ SHAPES = [
     ("LunarLander-128", 128, 8192, 8, 4, False, 128),
     ("HalfCheetah-128", 128, 4096, 17, 6, True, 128),
     ("Ant-64", 128, 4096, 105, 8, True, 64),
+    # the large heads (hidden 64, obs_dim <= 384, act_dim <= 32): Humanoid / HumanoidStandup
+    ("Humanoid-348", 128, 4096, 348, 17, True, 64),
+    ("Humanoid-376", 128, 4096, 376, 17, True, 64),
 ]
 PEAK_TF = 157.3
 
@@ -60,13 +70,14 @@ def kernel_times(agent, ro):
         return {"error": repr(e)}
 
 
-def run(label, T, Nn, D, A, cont, H, warmup, learns):
+def run(label, T, Nn, D, A, cont, H, warmup, learns, fused_loss=False):
     Cfg = diamond.ContinuousPPOConfig if cont else diamond.PPOConfig
     Agent = diamond.ContinuousPPO if cont else diamond.PPO
     cfg = Cfg(network_hidden_dim=H, rollout_steps=T, num_envs=Nn, verbose=False)
     torch.manual_seed(0)
     np.random.seed(0)
     agent = Agent(None, cfg, envs=SpecEnvs(D, A, cont))
+    agent.fused_loss = fused_loss   # the generic path's loss head in HIP; the fused path has none
     L = agent._learner
     ro, _ = synth(T, Nn, D, A, cont, seed=1)
     for _ in range(warmup):
@@ -82,6 +93,7 @@ def run(label, T, Nn, D, A, cont, H, warmup, learns):
     med = statistics.median(ms)
     out = {"label": label, "T": T, "N": Nn, "D": D, "A": A, "continuous": cont, "H": H,
            "fused": bool(L.fused), "shape_class": getattr(L, "shape_class", None),
+           "fused_loss": bool(fused_loss),
            "epochs": cfg.num_epochs, "minibatches": cfg.num_minibatches,
            "learns": learns, "warmup": warmup,
            "ms_median": med, "ms_min": min(ms), "ms_max": max(ms),
@@ -100,19 +112,43 @@ def run(label, T, Nn, D, A, cont, H, warmup, learns):
     return out
 
 
+def generic_child(label, warmup, learns, fused_loss):
+    """The shape's row from a fresh process with DPPO_WIDE=0: the generic path, unchanged code"""
+    cmd = [sys.executable, os.path.abspath(__file__), "--only", label, "--warmup", str(warmup),
+           "--learns", str(learns)] + (["--fused-loss"] if fused_loss else [])
+    r = subprocess.run(cmd, env=dict(os.environ, DPPO_WIDE="0"), capture_output=True, text=True,
+                       timeout=900)
+    if r.returncode != 0:
+        raise RuntimeError(f"generic child failed ({r.returncode}):\n{r.stdout}\n{r.stderr}")
+    row = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert not row["fused"] and row["fused_loss"] == fused_loss, row
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--learns", type=int, default=20)
-    ap.add_argument("--only", default=None, help="run one label")
+    ap.add_argument("--only", action="append", default=None, help="run this label (repeatable)")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="set the agents' fused_loss (it matters on the generic path only)")
+    ap.add_argument("--compare-generic", action="store_true",
+                    help="also time each shape's generic path in DPPO_WIDE=0 child processes")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "dppo_wide": os.environ.get("DPPO_WIDE"),
            "shapes": []}
     for s in SHAPES:
-        if a.only and s[0] != a.only:
+        if a.only and s[0] not in a.only:
             continue
-        r = run(*s, a.warmup, a.learns)
+        r = run(*s, a.warmup, a.learns, a.fused_loss)
+        if a.compare_generic:
+            r["generic"] = generic_child(s[0], a.warmup, a.learns, False)
+            r["generic_fused_loss"] = generic_child(s[0], a.warmup, a.learns, True)
+            fastest = min(r["generic"]["ms_min"], r["generic_fused_loss"]["ms_min"])
+            r["fused_max_below_generic_min"] = bool(r["fused"] and r["ms_max"] < fastest)
+            r["generic_median_over_fused_median"] = \
+                min(r["generic"]["ms_median"], r["generic_fused_loss"]["ms_median"]) / r["ms_median"]
         print(json.dumps(r), flush=True)
         res["shapes"].append(r)
     if a.out:

@@ -5,8 +5,9 @@ default torch sampling path.
     python tools/bench_wide_rollout.py --out profiles/wide_rollout.json
 
 Stub env (tests/golden/gym_stub.py: NumPy draws, no simulation, so the host side of a step is as
-cheap as an env gets), T = 32, N in {32, 1024, 8192}, two shapes: LunarLander-128 (D 8, 4 discrete
-actions, hidden 128) and Ant-64 (D 105, 8 Gaussian actions, hidden 64).  Per shape and N two
+cheap as an env gets), T = 32, N in {32, 1024, 8192}, three shapes: LunarLander-128 (D 8, 4 discrete
+actions, hidden 128), Ant-64 (D 105, 8 Gaussian actions, hidden 64) and Humanoid-64 (D 376, 17
+Gaussian actions, hidden 64: the large heads).  `--only NAME` runs one shape.  Per shape and N two
 agents with the same weights, the flag on and off, run their rollouts alternately (whatever else
 loads the host hits both alike): `--warmup` untimed rollouts each, then `--rollouts` timed ones,
 every one bracketed by a device synchronisation and the host wall clock.  Reported: the median ms
@@ -38,7 +39,8 @@ import gym_stub
 T = 32
 SIZES = [32, 1024, 8192]
 # (name, hidden, D, A, Gaussian head)
-SHAPES = [("LunarLander-128", 128, 8, 4, False), ("Ant-64", 64, 105, 8, True)]
+SHAPES = [("LunarLander-128", 128, 8, 4, False), ("Ant-64", 64, 105, 8, True),
+          ("Humanoid-64", 64, 376, 17, True)]
 
 
 class SampleClock:
@@ -118,9 +120,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rollouts", type=int, default=20)
+    ap.add_argument("--only", default=None, help="run one shape")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "runs": []}
     for name, Hd, D, A, cont in SHAPES:
+        if a.only and name != a.only:
+            continue
         for Nn in SIZES:
             r = run(name, Hd, D, A, cont, Nn, a.warmup, a.rollouts)
             print(json.dumps(r), flush=True)
