@@ -40,6 +40,7 @@ EXPORTED = [
     "dppo_gru_act_f32", "dppo_gru_value_f32", "dppo_gru_set_timing", "dppo_gru_get_timing",
     "dppo_gru_plan",
     "dppo_ppo_loss_f32", "dppo_policy_logp_f32", "dppo_ppo_loss_plan",
+    "dppo_gru_scan_plan", "dppo_gru_scan_fwd_f32", "dppo_gru_scan_bwd_f32",
 ]
 TIMING_CLASSES = ["eval", "gae", "adv_stats", "pack", "grad", "slab_reduce", "clip_adam",
                   "allreduce", "perm", "reduce_adam", "gae_probe"]
@@ -207,6 +208,9 @@ def load():
         "dppo_ppo_loss_f32": (ctypes.c_int, [P(LossArgs), vp]),
         "dppo_policy_logp_f32": (ctypes.c_int, [vp, vp, i32, vp, vp, i64, i64, i32, i32, vp, vp]),
         "dppo_ppo_loss_plan": (ctypes.c_int, [i64, i32, i32, P(i64), P(i32), P(i32)]),
+        "dppo_gru_scan_plan": (ctypes.c_int, [i32, i64, i64, P(i64)]),
+        "dppo_gru_scan_fwd_f32": (ctypes.c_int, [vp] * 7 + [i64, i64, i32, vp]),
+        "dppo_gru_scan_bwd_f32": (ctypes.c_int, [vp] * 10 + [i64, i64, i32, vp]),
         "dppo_set_timing": (ctypes.c_int, [vp, i32]),
         "dppo_get_timing": (ctypes.c_int, [vp, vp, vp]),
     }
@@ -259,6 +263,14 @@ def ppo_loss_plan(m: int, act_dim: int, continuous: bool = False):
     check(load().dppo_ppo_loss_plan(int(m), int(act_dim), int(bool(continuous)), ctypes.byref(ws),
                                     ctypes.byref(grid), ctypes.byref(cap)), "dppo_ppo_loss_plan")
     return ws.value, grid.value, cap.value
+
+
+def gru_scan_plan(G: int, T: int, N: int):
+    """(envs per workgroup, workgroups, floats of saved, of dgi, of dgh) of the GRU scan kernels
+    (dppo_gru_scan_fwd_f32 / dppo_gru_scan_bwd_f32); raises for an unsupported G, T < 1 or N < 1."""
+    out = (ctypes.c_int64 * 5)()
+    check(load().dppo_gru_scan_plan(int(G), int(T), int(N), out), "dppo_gru_scan_plan")
+    return tuple(out)
 
 
 def param_layout(dims: Dims) -> Layout:

@@ -66,13 +66,120 @@ class RecurrentPPOConfig:
     gae_bitexact: bool = True   # False: the chunked affine-scan GAE kernel (PPOConfig)
 
 
+CORE_SCAN_CALLS = [0]  # GRUCore forwards of this process that the scan kernels served
+_SCAN_WIDTHS = (16, 32, 64)
+
+
+class _FusedGRUScan(torch.autograd.Function):
+    """The GRU recurrence with per-step resets as an autograd node on the scan kernels
+    (csrc/gruseq.hip): forward = the input projection as one GEMM over [T N, I] and one
+    dppo_gru_scan_fwd_f32 launch; backward = one dppo_gru_scan_bwd_f32 launch and the five sums
+    over samples (dx, dWih, db_ih, dWhh, db_hh) as torch GEMMs / reductions.  Everything runs on
+    the current stream without a host synchronisation.  ``save`` False (inference): no per-sample
+    activations are kept."""
+
+    @staticmethod
+    def forward(ctx, x, hx0, dones, w_ih, w_hh, b_ih, b_hh, save):
+        T, Nn, I = x.shape
+        G = w_hh.shape[1]
+        dev = x.device
+        x2 = x.detach().reshape(T * Nn, I)
+        w_ih, w_hh, b_ih, b_hh = (t.detach().contiguous() for t in (w_ih, w_hh, b_ih, b_hh))
+        hx0 = hx0.detach().contiguous()
+        gi = torch.addmm(b_ih, x2, w_ih.t())
+        out = torch.empty((T, Nn, G), dtype=torch.float32, device=dev)
+        saved = torch.empty((T, Nn, 4 * G), dtype=torch.float32, device=dev) if save else None
+        N.check(N.load().dppo_gru_scan_fwd_f32(
+            gi.data_ptr(), hx0.data_ptr(), dones.data_ptr() if dones is not None else None,
+            w_hh.data_ptr(), b_hh.data_ptr(), out.data_ptr(),
+            saved.data_ptr() if save else None, T, Nn, G,
+            torch.cuda.current_stream(dev).cuda_stream), "dppo_gru_scan_fwd_f32")
+        CORE_SCAN_CALLS[0] += 1
+        if save:
+            ctx.save_for_backward(x2, hx0, w_ih, w_hh, saved, out)
+            ctx.dones = dones
+        ctx.set_materialize_grads(False)
+        # the final hidden state as a tensor of its own: a view of `out` could not carry the graph
+        return out, out[T - 1].unsqueeze(0).clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_hT):
+        x2, hx0, w_ih, w_hh, saved, out = ctx.saved_tensors
+        dones = ctx.dones
+        T, Nn, G = out.shape
+        dev = out.device
+        d_out = torch.zeros_like(out) if d_out is None else d_out.contiguous()
+        if d_hT is not None:
+            d_hT = d_hT.reshape(Nn, G).contiguous()
+        dgi = torch.empty((T * Nn, 3 * G), dtype=torch.float32, device=dev)
+        dgh = torch.empty((T * Nn, 3 * G), dtype=torch.float32, device=dev)
+        dh0 = torch.empty((Nn, G), dtype=torch.float32, device=dev)
+        N.check(N.load().dppo_gru_scan_bwd_f32(
+            d_out.data_ptr(), d_hT.data_ptr() if d_hT is not None else None, saved.data_ptr(),
+            out.data_ptr(), hx0.data_ptr(), dones.data_ptr() if dones is not None else None,
+            w_hh.data_ptr(), dgi.data_ptr(), dgh.data_ptr(), dh0.data_ptr(), T, Nn, G,
+            torch.cuda.current_stream(dev).cuda_stream), "dppo_gru_scan_bwd_f32")
+        need = ctx.needs_input_grad
+        dx = (dgi @ w_ih).reshape(T, Nn, -1) if need[0] else None
+        d_wih = dgi.t() @ x2 if need[3] else None
+        d_whh = None
+        if need[4]:
+            # the hidden state every step started from, after the reset: hp = h_prev * keep
+            hp = torch.cat([hx0.unsqueeze(0), out[:T - 1]], dim=0)
+            if dones is not None:
+                hp = hp * (dones == 0).to(torch.float32).unsqueeze(-1)
+            d_whh = dgh.t() @ hp.reshape(T * Nn, G)
+        return (dx, dh0 if need[1] else None, None, d_wih, d_whh,
+                dgi.sum(0) if need[5] else None, dgh.sum(0) if need[6] else None, None)
+
+
 class GRUCore(nn.GRU):
     """GRU with per-timestep hidden resets (intended semantics of recurrent_ppo.py:41-91)."""
 
     def __init__(self, input_dim: int, hidden_dim: int) -> None:
         super().__init__(input_dim, hidden_dim)
+        # True: forward() runs the recurrence on the scan kernels (csrc/gruseq.hip) where
+        # _scan_serves admits the call; the step loop below otherwise.  Off by default: the bits
+        # then differ from the loop's
+        self.fused_scan = False
+
+    def _scan_serves(self, x, hx, dones) -> bool:
+        """float32 CUDA input [T >= 1, N >= 1, I], hidden 16 / 32 / 64, and the module as
+        __init__ builds it: one layer, unidirectional, biases, no projection."""
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+                and x.shape[0] >= 1 and x.shape[1] >= 1 and x.shape[2] == self.input_size):
+            return False
+        if not (self.hidden_size in _SCAN_WIDTHS and self.num_layers == 1
+                and not self.bidirectional and self.bias and not self.batch_first
+                and getattr(self, "proj_size", 0) == 0):
+            return False
+        w = self.weight_hh_l0
+        if w.dtype != torch.float32 or w.device != x.device:
+            return False
+        if hx is not None and not (hx.dtype == torch.float32 and hx.device == x.device
+                                   and hx.numel() == x.shape[1] * self.hidden_size):
+            return False
+        return dones is None or (dones.device == x.device and dones.dim() == 2
+                                 and tuple(dones.shape) == tuple(x.shape[:2]))
+
+    def _forward_scan(self, x, hx, dones):
+        T, Nn = x.shape[:2]
+        G = self.hidden_size
+        if hx is None:
+            hx0 = torch.zeros(Nn, G, dtype=x.dtype, device=x.device)
+        else:
+            hx0 = hx.reshape(Nn, G)
+        if dones is not None:
+            dones = (dones if dones.dtype == torch.bool else dones.bool()).contiguous()
+            dones = dones.view(torch.uint8)
+        params = (self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0)
+        save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, hx0) + params)
+        return _FusedGRUScan.apply(x.contiguous(), hx0, dones, *params, save)
 
     def forward(self, x, hx=None, dones=None):
+        if getattr(self, "fused_scan", False) and self._scan_serves(x, hx, dones):
+            return self._forward_scan(x, hx, dones)
         seq_length, batch_size = x.shape[:2]
         if hx is None:
             hx = torch.zeros(1, batch_size, self.hidden_size, dtype=x.dtype, device=x.device)
@@ -148,6 +255,12 @@ class RecurrentPPO:
     # and its backward from the loss-head kernel (engine.fused_ppo_loss, csrc/losshead.hip)
     # instead of the torch op chain; the network stays under autograd.  Off by default
     fused_loss = False
+    # the torch learn loop and the torch rollout run every GRUCore of the network on the GRU scan
+    # kernels (GRUCore.fused_scan, csrc/gruseq.hip): one launch for the whole forward sequence and
+    # one for the BPTT instead of T cell launches each way; the rest of the network stays under
+    # autograd.  Where fused_gru / fused_rollout serve the agent they win as before.  Off by
+    # default: the bits then differ from nn.GRU's
+    fused_core = False
 
     def __init__(self, env_fn: Callable[[], Any], cfg: RecurrentPPOConfig = RecurrentPPOConfig(),
                  network_cls: Any = RecurrentActorCriticNetwork, envs=None) -> None:
@@ -188,6 +301,7 @@ class RecurrentPPO:
                 raise RuntimeError("RecurrentActorCriticNetwork layout differs from libdppo's")
         self.last_losses = None
         self.loss_head_calls = 0  # minibatches whose loss the loss-head kernel computed (fused_loss)
+        self.core_scan_calls = 0  # GRUCore forwards the scan kernels served (fused_core)
         # the fused rollout's Philox key (mixed as _AgentBase._act_seed) and call counter
         base_seed = cfg.seed if cfg.seed is not None else torch.initial_seed()
         self._act_seed = (int(base_seed) * 0x9E3779B97F4A7C15 + rank) & (2 ** 64 - 1)
@@ -208,10 +322,20 @@ class RecurrentPPO:
         self.ticker = Ticker(cfg.total_steps, cfg.num_envs, cfg.rollout_steps, verbose=cfg.verbose)
         self.cfg = cfg
 
+    def _set_core_scan(self) -> bool:
+        """Hand ``fused_core`` to every GRUCore of the network (before a torch-path use)."""
+        on = bool(self.fused_core)
+        for m in self.network.modules():
+            if isinstance(m, GRUCore):
+                m.fused_scan = on
+        return on
+
     def rollout(self):
         """recurrent_ppo.py:205-263 with tensor-safe hidden-state handling."""
         if self.fused_rollout and self.gru is not None:
             return self._rollout_fused()
+        self._set_core_scan()
+        scans0 = CORE_SCAN_CALLS[0]
         experience = []
         observations, hx, prev_dones = self.current_observations, self.current_hx, self.prev_dones
         for _ in range(self.cfg.rollout_steps):
@@ -236,6 +360,7 @@ class RecurrentPPO:
             if self.ticker is not None:
                 self.ticker.tick(rewards, dones)
         self.current_observations, self.current_hx, self.prev_dones = observations, hx, prev_dones
+        self.core_scan_calls += CORE_SCAN_CALLS[0] - scans0
         return experience
 
     def _rollout_fused(self):
@@ -368,6 +493,10 @@ class RecurrentPPO:
             self.lr_scheduler.step()
             return
         fused_loss = bool(self.fused_loss)
+        # with fused_core the loop records {loss, policy, value, entropy} per minibatch (this
+        # rank's means), as the fused learn does
+        record = [] if self._set_core_scan() else None
+        scans0 = CORE_SCAN_CALLS[0]
         if fused_loss:
             act32 = actions.to(torch.int32).contiguous()
             old_lp, adv_c, ret_c = (x.float().contiguous() for x in
@@ -379,12 +508,14 @@ class RecurrentPPO:
                 nl, nv = flatten(nl)[mb_idx], flatten(nv)[mb_idx]
                 if fused_loss:
                     calls0 = LOSS_KERNEL_CALLS[0]
-                    loss, _ = fused_ppo_loss(
+                    loss, terms = fused_ppo_loss(
                         nl, nv, None, actions=act32, old_log_probs=old_lp, advantages=adv_c,
                         returns=ret_c, idx=mb_idx, clip=cfg.ppo_clip,
                         value_loss_weight=cfg.value_loss_weight, entropy_beta=cfg.entropy_beta,
                         scale=1.0 / world if world > 1 else 1.0, continuous=False)
                     self.loss_head_calls += LOSS_KERNEL_CALLS[0] - calls0
+                    if record is not None:
+                        record.append(terms[:4].clone())
                 else:
                     dist = torch.distributions.Categorical(logits=nl)
                     ratio = (dist.log_prob(actions[mb_idx]) - log_probs[mb_idx]).exp()
@@ -393,6 +524,8 @@ class RecurrentPPO:
                                                                   1 + cfg.ppo_clip)).mean()
                     l_v = 0.5 * torch.nn.functional.mse_loss(nv, returns[mb_idx])
                     loss = l_pi + cfg.value_loss_weight * l_v - cfg.entropy_beta * dist.entropy().mean()
+                    if record is not None:
+                        record.append(torch.stack([loss, l_pi, l_v, dist.entropy().mean()]).detach())
                     if world > 1:
                         # local mean x 1/world, summed over the ranks = the union minibatch's mean
                         loss = loss * (1.0 / world)
@@ -404,6 +537,11 @@ class RecurrentPPO:
                     self.flat.flat.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(),
                     self.v.data_ptr(), self.flat.total, cfg.grad_norm_clip, float(lr), 0.9, 0.999,
                     cfg.adam_eps, step, None, stream), "dppo_clip_adam_f32")
+        self.core_scan_calls += CORE_SCAN_CALLS[0] - scans0
+        if record is not None:
+            self.last_losses = torch.stack(record)
+            if fused_loss and world > 1:   # the kernel's loss carries the rank's 1 / world share
+                self.last_losses[:, 0] *= float(world)
         advance_adam_steps(self.optimizer, self.flat, cfg.num_epochs * cfg.num_minibatches)
         self.lr_scheduler.step()
 

@@ -593,6 +593,42 @@ int dppo_policy_logp_f32(const float* logits, const float* log_std, int32_t log_
 int dppo_ppo_loss_plan(int64_t m, int32_t act_dim, int32_t continuous, int64_t* workspace_floats,
                        int32_t* grid, int32_t* max_A);
 
+/* ---- GRU recurrence for a network that runs under the caller's autograd (GRUCore inside a
+ * custom network_cls, shapes outside the fused GRU classes): the whole forward sequence and the
+ * whole BPTT of recurrent_ppo.py:41-91 (a torch GRU cell stepped over t, the hidden state zeroed
+ * where dones[t], :82-87) as one launch each.  The input projection gi = x Wih^T + b_ih and the
+ * weight-gradient sums stay with the caller (GEMMs over [T N, .]), so any input width is served.
+ * Handle-less, stream-ordered, allocates nothing, no host synchronisation, no floating-point
+ * atomics: the same inputs give the same bits.  G = gru hidden, 16, 32 or 64. */
+
+/* Host only.  out[5] = {envs per workgroup (256 / G), workgroups (ceil(N / envs)), floats of
+ * `saved` (T N 4G), of `dgi` (T N 3G), of `dgh` (T N 3G)}; out may be NULL.  DPPO_EUNSUPPORTED for
+ * another G, DPPO_EINVAL for T < 1 or N < 1.  No reference counterpart. */
+int dppo_gru_scan_plan(int32_t G, int64_t T, int64_t N, int64_t* out);
+
+/* Forward over t = 0 .. T-1 from hx0 (recurrent_ppo.py:41-91; gate order r, z, n as torch's GRU):
+ *   hp = dones[t][n] ? 0 : h;  gh = Whh hp + b_hh;  r = s(gi_r + gh_r);  z = s(gi_z + gh_z);
+ *   n = tanh(gi_n + r gh_n);  h = (1 - z) n + z hp
+ * gi [T][N][3G], hx0 [N][G], dones [T][N] bytes (NULL: none), Whh [3G][G] 16-byte aligned,
+ * b_hh [3G]; out [T][N][G] (the last step is the final hidden state); saved [T][N][4G] = r, z, n,
+ * gh_n per sample for dppo_gru_scan_bwd_f32, or NULL (inference: nothing saved, the same out
+ * bits).  DPPO_EINVAL, without a launch, for T < 1, N < 1, a NULL required pointer or a
+ * misaligned one; DPPO_EUNSUPPORTED for another G. */
+int dppo_gru_scan_fwd_f32(const float* gi, const float* hx0, const uint8_t* dones,
+                          const float* Whh, const float* b_hh, float* out, float* saved,
+                          int64_t T, int64_t N, int32_t G, void* stream);
+
+/* Backward through time of the scan above (autograd's backward of recurrent_ppo.py:41-91), t =
+ * T-1 .. 0: dout [T][N][G] and dh_T [N][G] (NULL: 0) are the gradients of out and of the final
+ * hidden state; saved, out, hx0, dones, Whh as the forward had them.  Writes dgi [T][N][3G] (the
+ * gradient of gi), dgh [T][N][3G] (of gh = Whh hp + b_hh) and dh0 [N][G] (of hx0).  The caller
+ * forms dx = dgi Wih, dWih = dgi^T x, db_ih = sum dgi, dWhh = dgh^T hp, db_hh = sum dgh.
+ * Validation as the forward's. */
+int dppo_gru_scan_bwd_f32(const float* dout, const float* dh_T, const float* saved,
+                          const float* out, const float* hx0, const uint8_t* dones,
+                          const float* Whh, float* dgi, float* dgh, float* dh0, int64_t T,
+                          int64_t N, int32_t G, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
