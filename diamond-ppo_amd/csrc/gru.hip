@@ -5,7 +5,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "grucell.h"
 
 // ---------------------------------------------------------------------------------------------
 // C ABI (include/dppo.h): handle = workspace for one rollout shape.
@@ -37,18 +37,13 @@ struct dppo_gru_handle {
 
 namespace {
 
-constexpr int kH = 64;     // MLP hidden
-constexpr int kAPad = 16;  // action dims padded
-
 int gru_validate(const dppo_gru_dims* d) {
   if (!d || d->rollout_steps < 1 || d->num_envs < 1 || d->obs_dim < 1 || d->act_dim < 1 ||
       d->gru_hidden < 1) {
     set_error("invalid dppo_gru_dims");
     return DPPO_EINVAL;
   }
-  const int G = d->gru_hidden;
-  if (d->hidden != kH || !(G == 16 || G == 32 || G == 64) || d->obs_dim > 32 ||
-      d->act_dim > kAPad) {
+  if (d->hidden != kH || !gru_width_ok(d->gru_hidden) || d->obs_dim > 32 || d->act_dim > kAPad) {
     set_error("fused GRU kernels support hidden=64, gru_hidden in {16, 32, 64}, obs_dim<=32, "
               "act_dim<=16 "
               "(got H=%d G=%d D=%d A=%d)", d->hidden, d->gru_hidden, d->obs_dim, d->act_dim);

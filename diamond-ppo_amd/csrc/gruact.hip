@@ -21,14 +21,12 @@
 // position in the batch and on any grid.  Lanes past n clamp to env n - 1 (valid addresses) and
 // store nothing.  The Philox key, counter and per-env counter layout are the same at every width:
 // the stream does not depend on G.
-#include "common.h"
+#include "grucell.h"
 #include "philox.h"
 
 namespace dppo {
 namespace {
 
-constexpr int kH = 64;     // MLP hidden
-constexpr int kAPad = 16;  // action dims padded
 constexpr int kEnvsPerWg = 4;
 
 struct GruStepArgs {
@@ -297,13 +295,9 @@ int launch_step(int G, bool act, const GruOffsets& po, const float* params,
   a.seed_hi = (uint32_t)(seed >> 32);
   a.ctr_lo = (uint32_t)counter;
   a.ctr_hi = (uint32_t)(counter >> 32);
-  switch (G) {
-    case 16: launch_width<16>(act, grid, a, s); break;
-    case 32: launch_width<32>(act, grid, a, s); break;
-    case 64: launch_width<64>(act, grid, a, s); break;
-    default:
-      set_error("no wide GRU rollout kernel for gru_hidden=%d", G);
-      return DPPO_EUNSUPPORTED;
+  if (!dispatch_gru_width(G, [&](auto g) { launch_width<decltype(g)::value>(act, grid, a, s); })) {
+    set_error("no wide GRU rollout kernel for gru_hidden=%d", G);
+    return DPPO_EUNSUPPORTED;
   }
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;

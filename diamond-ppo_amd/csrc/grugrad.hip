@@ -31,17 +31,14 @@
 //
 // LDS holds the biases for the whole launch and, in one region restaged between the phases' own
 // barriers, only the weights the current phase reads: A Wb + Wih | B, D Whh | C Wa1 Wc1 Wa2 |
-// E Wih.  Whh is staged with a row stride of G + 1 floats: lane j's k-th read of its rows in B
-// ((gG + j)(G + 1) + k) and its column reads in D (g (G + 1) + j) both fall on 64 (or 2 x 32
-// pairwise equal) distinct consecutive banks.
-#include "common.h"
+// E Wih.  The recurrences of B and D, and Whh's LDS image with its row stride of G + 1 floats, are
+// grucell.h's, shared with the scan kernels of gruseq.hip.
+#include "grucell.h"
 
 namespace dppo {
 namespace {
 
-constexpr int kH = 64;     // MLP hidden
 constexpr int kThr = 256;
-constexpr int kAPad = 16;  // action dims padded
 constexpr int kGiBlk = 48; // gate rows per register block of phase A
 
 // LDS (floats): the phase's weights at W, then the biases, then the exchange buffers
@@ -75,11 +72,43 @@ __device__ __forceinline__ void stage4(float* dst, const float* __restrict__ src
   for (int k = tid; k < n / 4; k += kThr) ((f32x4*)dst)[k] = ((const f32x4*)src)[k];
 }
 
-// Whh [3G][G] with a row stride of G + 1
+// Phases B and D for lane j of env n: where grucell.h's recurrences find their operands, the SoA
+// scratch rows of sample i = t N + n.
 template <int G>
-__device__ __forceinline__ void stage_whh(float* dst, const float* __restrict__ src, int tid) {
-  for (int k = tid; k < 3 * G * G; k += kThr) dst[(k / G) * (G + 1) + (k % G)] = src[k];
-}
+struct GradFwdOps {
+  const GruScratch& sc;
+  const uint8_t* dones;
+  int N, n, j;
+  __device__ __forceinline__ GruFwdIn in(int t) const {
+    const int64_t i = (int64_t)t * N + n;
+    const float* gi = sc.gi + i * (3 * G);
+    return GruFwdIn{gi[j], gi[G + j], gi[2 * G + j], dones[i] != 0};
+  }
+  __device__ __forceinline__ void store(int t, float hin, float r, float z, float nn, float ghn,
+                                        float hout) const {
+    const int64_t i = (int64_t)t * N + n;
+    sc.hi[i * G + j] = hin;
+    sc.r[i * G + j] = r;
+    sc.z[i * G + j] = z;
+    sc.n[i * G + j] = nn;
+    sc.ghn[i * G + j] = ghn;
+    sc.ho[i * G + j] = hout;
+  }
+};
+template <int G>
+struct GradBwdOps {
+  const GruScratch& sc;
+  const uint8_t* dones;
+  int N, n, j;
+  __device__ __forceinline__ GruBwdIn in(int t) const {
+    const int64_t i = (int64_t)t * N + n;
+    return GruBwdIn{sc.dho[i * G + j], sc.r[i * G + j], sc.z[i * G + j], sc.n[i * G + j],
+                    sc.ghn[i * G + j], sc.hi[i * G + j], dones[i] != 0};
+  }
+  __device__ __forceinline__ int64_t row(int t) const { return ((int64_t)t * N + n) * (3 * G); }
+  __device__ __forceinline__ float* dgi(int t) const { return sc.dgi + row(t); }
+  __device__ __forceinline__ float* dgh(int t) const { return sc.dgh + row(t); }
+};
 
 // Sum over k = samples of A[s][m] B[s][n] for one 16 x 16 output tile: rows mt*16.., cols nt*16..
 // of arrays with row strides lda / ldb (floats).  Lane (q, r) supplies A[s_{4kk+q}][16mt + r] and
@@ -125,7 +154,7 @@ __device__ __forceinline__ f32x4 tile_sum(const float* __restrict__ A, int lda, 
 
 template <int G>
 __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
-  constexpr int kEnvs = kThr / G, G3 = 3 * G, kWs = G + 1;
+  constexpr int kEnvs = kThr / G, G3 = 3 * G;
   static_assert(G3 % kGiBlk == 0 && G3 <= kThr && G % 16 == 0, "gate blocking");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const GruLds L = gru_lds(a.D, G);
@@ -240,60 +269,19 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
     }
   }
   __syncthreads();
-  stage_whh<G>(W, P + po.Whh, tid);
+  // 16-byte loads, as stage4's: params is 16-byte aligned (checked at the C ABI) and every
+  // offset of the layout is a multiple of 16 floats (gru_layout)
+  stage_whh<G, kThr>(W, P + po.Whh, tid);
   __syncthreads();
 
-  // ---- B: forward recurrence, lane j of env e = hidden unit j (G lanes of one wave per env)
+  // ---- B: forward recurrence (grucell.h), lane j of env e = hidden unit j (G lanes of one wave
+  // per env)
   const int e = tid / G, j = tid % G;
   const bool env_ok = e < ne;
   const int n = n0 + e;
-  if (env_ok) {
-    const float* wr = W + j * kWs;
-    const float* wz = W + (G + j) * kWs;
-    const float* wn = W + (2 * G + j) * kWs;
-    const float br = lds[L.bhh + j], bz = lds[L.bhh + G + j], bn = lds[L.bhh + 2 * G + j];
-    float h = a.b.hx0[(int64_t)n * G + j];
-    float* hb = lds + L.hbuf + e * G;
-    // the next step's inputs are loaded a step ahead (they do not depend on h)
-    float gir_n = sc.gi[(int64_t)n * G3 + j], giz_n = sc.gi[(int64_t)n * G3 + G + j],
-          gin_n = sc.gi[(int64_t)n * G3 + 2 * G + j];
-    uint8_t done_n = a.b.prev_dones[n];
-    for (int t = 0; t < T; ++t) {
-      const int64_t i = (int64_t)t * N + n;
-      const float gir = gir_n, giz = giz_n, gin = gin_n;
-      const bool done = done_n;
-      {
-        const int64_t in = (int64_t)min(t + 1, T - 1) * N + n;
-        gir_n = sc.gi[in * G3 + j];
-        giz_n = sc.gi[in * G3 + G + j];
-        gin_n = sc.gi[in * G3 + 2 * G + j];
-        done_n = a.b.prev_dones[in];
-      }
-      if (done) h = 0.0f;  // hx[:, dones[t]] = 0 (recurrent_ppo.py:84)
-      hb[j] = h;
-      float ghr = br, ghz = bz, ghn = bn;
-#pragma unroll
-      for (int q = 0; q < G / 4; ++q) {
-        const f32x4 x = *(const f32x4*)(hb + 4 * q);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          ghr += wr[4 * q + u] * x[u];
-          ghz += wz[4 * q + u] * x[u];
-          ghn += wn[4 * q + u] * x[u];
-        }
-      }
-      const float r = sigm(gir + ghr), z = sigm(giz + ghz);
-      const float nn = tanh_acc(gin + r * ghn);
-      const float hn = (1.0f - z) * nn + z * h;
-      sc.hi[i * G + j] = h;
-      sc.r[i * G + j] = r;
-      sc.z[i * G + j] = z;
-      sc.n[i * G + j] = nn;
-      sc.ghn[i * G + j] = ghn;
-      sc.ho[i * G + j] = hn;
-      h = hn;
-    }
-  }
+  if (env_ok)
+    gru_seq_fwd<G>(W, lds + L.bhh, lds + L.hbuf + e * G, j, a.b.hx0[(int64_t)n * G + j], T,
+                   GradFwdOps<G>{sc, a.b.prev_dones, N, n, j});
   __syncthreads();
   float* Wa1 = W;
   float* Wc1 = W + kH * G;
@@ -459,60 +447,13 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
     for (int k = 1; k < kAPad / 4; ++k) ((f32x4*)(sc.dv + i * kAPad))[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   __syncthreads();
-  stage_whh<G>(W, P + po.Whh, tid);
+  stage_whh<G, kThr>(W, P + po.Whh, tid);
   __syncthreads();
 
   // ---- D: BPTT, reverse in t (lane j of env e reads column j of Whh)
-  if (env_ok) {
-    const float* wc = W + j;
-    float* gb = lds + L.gbuf + e * G3;
-    float carry = 0.0f;
-    // the earlier step's saved activations are loaded a step ahead (they do not depend on carry)
-    struct Saved {
-      float dho, z, n, r, hi, ghn;
-      uint8_t done;
-    };
-    auto load = [&](int t) {
-      const int64_t i = (int64_t)t * N + n;
-      return Saved{sc.dho[i * G + j], sc.z[i * G + j], sc.n[i * G + j], sc.r[i * G + j],
-                   sc.hi[i * G + j], sc.ghn[i * G + j], a.b.prev_dones[i]};
-    };
-    Saved nx = load(T - 1);
-    for (int t = T - 1; t >= 0; --t) {
-      const int64_t i = (int64_t)t * N + n;
-      const Saved cur = nx;
-      nx = load(max(t - 1, 0));
-      const float dh = cur.dho + carry;
-      const float z = cur.z, nn = cur.n, r = cur.r;
-      const float hin = cur.hi, ghn = cur.ghn;
-      const float dn = dh * (1.0f - z);
-      const float dz = dh * (hin - nn);
-      const float dnp = dn * (1.0f - nn * nn);
-      const float dghn = dnp * r;
-      const float drp = dnp * ghn * r * (1.0f - r);
-      const float dzp = dz * z * (1.0f - z);
-      float* dgi = sc.dgi + i * G3;
-      float* dgh = sc.dgh + i * G3;
-      dgi[j] = drp;
-      dgi[G + j] = dzp;
-      dgi[2 * G + j] = dnp;
-      dgh[j] = drp;
-      dgh[G + j] = dzp;
-      dgh[2 * G + j] = dghn;
-      gb[j] = drp;
-      gb[G + j] = dzp;
-      gb[2 * G + j] = dghn;
-      float dhin = dh * z;
-#pragma unroll
-      for (int q = 0; q < G3 / 4; ++q) {
-        const f32x4 x = *(const f32x4*)(gb + 4 * q);
-        dhin += wc[(4 * q) * kWs] * x[0] + wc[(4 * q + 1) * kWs] * x[1] +
-                wc[(4 * q + 2) * kWs] * x[2] + wc[(4 * q + 3) * kWs] * x[3];
-      }
-      // h_in = h_prev * keep  =>  dh_prev = dh_in * keep
-      carry = cur.done ? 0.0f : dhin;
-    }
-  }
+  if (env_ok)
+    gru_seq_bwd<G>(W, lds + L.gbuf + e * G3, j, 0.0f, T,
+                   GradBwdOps<G>{sc, a.b.prev_dones, N, n, j});
   __syncthreads();
   stage4(W, P + po.Wih, G3 * kH, tid);
   __syncthreads();
@@ -695,14 +636,12 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
   a.slabs = slabs;
   a.slab_stride = slab_stride;
   a.p_total = p_total;
-  switch (G) {
-    case 16: return launch_g<16>(a, s);
-    case 32: return launch_g<32>(a, s);
-    case 64: return launch_g<64>(a, s);
-    default:
-      set_error("no GRU gradient kernel for gru_hidden=%d", G);
-      return DPPO_EUNSUPPORTED;
+  int rc = DPPO_OK;
+  if (!dispatch_gru_width(G, [&](auto g) { rc = launch_g<decltype(g)::value>(a, s); })) {
+    set_error("no GRU gradient kernel for gru_hidden=%d", G);
+    return DPPO_EUNSUPPORTED;
   }
+  return rc;
 }
 
 }  // namespace dppo

@@ -299,12 +299,36 @@ class RolloutStager:
         self.slots[self.cur]["released"] = ev
 
 
-def hparams(cfg, lr: float, adam_step: int, betas=(0.9, 0.999)) -> N.HParams:
+ADAM_BETAS = (0.9, 0.999)   # torch.optim.Adam's defaults, which the agents never change
+
+
+def hparams(cfg, lr: float, adam_step: int, betas=ADAM_BETAS) -> N.HParams:
     return N.HParams(gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, ppo_clip=cfg.ppo_clip,
                      value_loss_weight=cfg.value_loss_weight, entropy_beta=cfg.entropy_beta,
                      grad_norm_clip=cfg.grad_norm_clip, adam_beta1=betas[0], adam_beta2=betas[1],
                      adam_eps=cfg.adam_eps, advantage_norm=int(bool(cfg.advantage_norm)),
                      lr=float(lr), adam_step=int(adam_step))
+
+
+def clip_adam(flat: "FlatParams", m, v, cfg, lr: float, step: int, stream) -> None:
+    """clip_grad_norm_ + Adam step number ``step`` on the flat parameters from ``flat.grad``
+    (dppo_clip_adam_f32, stream-ordered)."""
+    N.check(N.load().dppo_clip_adam_f32(
+        flat.flat.data_ptr(), flat.grad.data_ptr(), m.data_ptr(), v.data_ptr(), flat.total,
+        cfg.grad_norm_clip, float(lr), *ADAM_BETAS, cfg.adam_eps, step, None, stream),
+        "dppo_clip_adam_f32")
+
+
+def broadcast_flat(flat: "FlatParams") -> None:
+    """Replicate rank 0's flat parameters (identical seeds make this a no-op in practice); through
+    the CPU unless the backend is nccl."""
+    d = torch.distributed
+    if d.get_backend() == "nccl":
+        d.broadcast(flat.flat, src=0)
+    else:
+        cpu = flat.flat.cpu()
+        d.broadcast(cpu, src=0)
+        flat.flat.copy_(cpu)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -376,13 +400,11 @@ def fused_shape_class(hidden: int, obs_dim: int, act_dim: int, world: int = 1,
     return None
 
 
-def _torch_ppo_loss(logits, values, log_std, actions, old_log_probs, advantages, returns, idx,
-                    clip, value_loss_weight, entropy_beta, scale, continuous):
-    """The reference's minibatch loss as torch ops (ppo.py:264-280, continuous_ppo.py:276-292):
-    what ``fused_ppo_loss`` computes, and its fallback for inputs the kernel does not serve."""
-    if idx is not None:
-        actions, old_log_probs = actions[idx], old_log_probs[idx]
-        advantages, returns = advantages[idx], returns[idx]
+def torch_ppo_terms(logits, values, log_std, actions, old_log_probs, advantages, returns, clip,
+                    value_loss_weight, entropy_beta, continuous):
+    """The reference's minibatch loss as torch ops (ppo.py:264-280, continuous_ppo.py:276-292) on
+    the minibatch's own rows: ``(loss, l_pi, l_v, entropy, ratio)``.  The one statement of these
+    terms for every torch learn loop."""
     if continuous:
         from .continuous_ppo import JointNormal
         dist = JointNormal(loc=logits, scale=log_std.exp())
@@ -395,7 +417,19 @@ def _torch_ppo_loss(logits, values, log_std, actions, old_log_probs, advantages,
                      -advantages * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
     l_v = 0.5 * torch.nn.functional.mse_loss(values, returns)
     ent = dist.entropy().mean()
-    loss = l_pi + value_loss_weight * l_v + -entropy_beta * ent
+    return l_pi + value_loss_weight * l_v + -entropy_beta * ent, l_pi, l_v, ent, ratio
+
+
+def _torch_ppo_loss(logits, values, log_std, actions, old_log_probs, advantages, returns, idx,
+                    clip, value_loss_weight, entropy_beta, scale, continuous):
+    """``torch_ppo_terms`` with ``fused_ppo_loss``'s operands and results: what the kernel
+    computes, and its fallback for inputs it does not serve."""
+    if idx is not None:
+        actions, old_log_probs = actions[idx], old_log_probs[idx]
+        advantages, returns = advantages[idx], returns[idx]
+    loss, l_pi, l_v, ent, ratio = torch_ppo_terms(
+        logits, values, log_std, actions, old_log_probs, advantages, returns, clip,
+        value_loss_weight, entropy_beta, continuous)
     if scale != 1.0:
         loss = loss * scale
     with torch.no_grad():
@@ -699,13 +733,7 @@ class NativeLearner:
             self.handle.comm_init(self.world, self.rank, obj[0])
         if mode == "peer" or (mode == "auto" and 1 < self.world <= 8):
             self.peer = self._init_peer(d, required=mode == "peer")
-        # replicate rank 0's initial parameters (identical seeds make this a no-op in practice)
-        if d.get_backend() == "nccl":
-            d.broadcast(self.flat.flat, src=0)
-        else:
-            cpu = self.flat.flat.cpu()
-            d.broadcast(cpu, src=0)
-            self.flat.flat.copy_(cpu)
+        broadcast_flat(self.flat)
 
     def _all_ranks(self, d, ok: bool) -> bool:
         dev = self.device if d.get_backend() == "nccl" else "cpu"
@@ -1142,17 +1170,14 @@ class NativeLearner:
                     if self.world > 1:
                         torch.distributed.all_reduce(self.flat.grad)
                     step += 1
-                    N.check(lib.dppo_clip_adam_f32(
-                        self.flat.flat.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(),
-                        self.v.data_ptr(), self.flat.total, cfg.grad_norm_clip, float(lr), 0.9,
-                        0.999, cfg.adam_eps, step, None, stream), "dppo_clip_adam_f32")
+                    clip_adam(self.flat, self.m, self.v, cfg, lr, step, stream)
                     continue
+                if self.continuous:
+                    hd, ls_, new_v = net.get_means_log_stds_and_values(obs[mb_idx])
+                else:
+                    (hd, new_v), ls_ = net.get_logits_and_values(obs[mb_idx]), None
                 if fused_loss:
                     # the kernel reads acts / log_probs / adv / ret through mb_idx itself
-                    if self.continuous:
-                        hd, ls_, new_v = net.get_means_log_stds_and_values(obs[mb_idx])
-                    else:
-                        (hd, new_v), ls_ = net.get_logits_and_values(obs[mb_idx]), None
                     calls0 = LOSS_KERNEL_CALLS[0]
                     loss, _ = fused_ppo_loss(
                         hd, new_v, ls_, actions=acts, old_log_probs=log_probs, advantages=adv,
@@ -1161,29 +1186,13 @@ class NativeLearner:
                         scale=share if self.world > 1 else 1.0, continuous=self.continuous)
                     self.loss_head_calls += LOSS_KERNEL_CALLS[0] - calls0
                 else:
-                    if self.continuous:
-                        from .continuous_ppo import JointNormal
-                        m_, ls_, v_ = net.get_means_log_stds_and_values(obs[mb_idx])
-                        dist = JointNormal(loc=m_, scale=ls_.exp())
-                        new_v = v_
-                    else:
-                        lg, new_v = net.get_logits_and_values(obs[mb_idx])
-                        dist = torch.distributions.Categorical(logits=lg)
-                    new_lp = dist.log_prob(acts[mb_idx])
-                    ratio = (new_lp - log_probs[mb_idx]).exp()
-                    a_mb = adv[mb_idx]
-                    l_pi = torch.max(-a_mb * ratio, -a_mb * torch.clamp(
-                        ratio, 1.0 - cfg.ppo_clip, 1.0 + cfg.ppo_clip)).mean()
-                    l_v = 0.5 * torch.nn.functional.mse_loss(new_v, ret[mb_idx])
-                    ent = dist.entropy().mean()
-                    loss = l_pi + cfg.value_loss_weight * l_v + -cfg.entropy_beta * ent
+                    loss = torch_ppo_terms(
+                        hd, new_v, ls_, acts[mb_idx], log_probs[mb_idx], adv[mb_idx], ret[mb_idx],
+                        cfg.ppo_clip, cfg.value_loss_weight, cfg.entropy_beta, self.continuous)[0]
                     if self.world > 1:
                         loss = loss * share
                 loss.backward()
                 if self.world > 1:
                     torch.distributed.all_reduce(self.flat.grad)
                 step += 1
-                N.check(lib.dppo_clip_adam_f32(
-                    self.flat.flat.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(),
-                    self.v.data_ptr(), self.flat.total, cfg.grad_norm_clip, float(lr), 0.9, 0.999,
-                    cfg.adam_eps, step, None, stream), "dppo_clip_adam_f32")
+                clip_adam(self.flat, self.m, self.v, cfg, lr, step, stream)

@@ -34,7 +34,8 @@ import torch.nn as nn
 from . import _native as N
 from ._spaces import is_box, is_discrete, make_vector_env
 from .engine import FlatParams, bind_adam_state, adam_step_count, advance_adam_steps, \
-    dist_world, fused_ppo_loss, require_gpu, LOSS_KERNEL_CALLS
+    broadcast_flat, clip_adam, dist_world, fused_ppo_loss, hparams, require_gpu, \
+    torch_ppo_terms, LOSS_KERNEL_CALLS
 from .utils import Checkpointer, Logger, Ticker, Timer
 
 
@@ -309,14 +310,8 @@ class RecurrentPPO:
         self._rollout_staging = None
         if not getattr(cfg, "gae_bitexact", True):
             self.handle.set_gae_mode(N.GAE_AFFINE)
-        if world > 1:   # replicate rank 0's initial weights (identical seeds: a no-op in practice)
-            d = torch.distributed
-            if d.get_backend() == "nccl":
-                d.broadcast(self.flat.flat, src=0)
-            else:
-                cpu = self.flat.flat.cpu()
-                d.broadcast(cpu, src=0)
-                self.flat.flat.copy_(cpu)
+        if world > 1:
+            broadcast_flat(self.flat)
         self.logger, self.timer = Logger(), Timer()
         self.checkpointer = Checkpointer(folder="models", run_name="default")
         self.ticker = Ticker(cfg.total_steps, cfg.num_envs, cfg.rollout_steps, verbose=cfg.verbose)
@@ -517,15 +512,12 @@ class RecurrentPPO:
                     if record is not None:
                         record.append(terms[:4].clone())
                 else:
-                    dist = torch.distributions.Categorical(logits=nl)
-                    ratio = (dist.log_prob(actions[mb_idx]) - log_probs[mb_idx]).exp()
-                    a = advantages[mb_idx]
-                    l_pi = torch.max(-a * ratio, -a * torch.clamp(ratio, 1 - cfg.ppo_clip,
-                                                                  1 + cfg.ppo_clip)).mean()
-                    l_v = 0.5 * torch.nn.functional.mse_loss(nv, returns[mb_idx])
-                    loss = l_pi + cfg.value_loss_weight * l_v - cfg.entropy_beta * dist.entropy().mean()
+                    loss, l_pi, l_v, ent, _ = torch_ppo_terms(
+                        nl, nv, None, actions[mb_idx], log_probs[mb_idx], advantages[mb_idx],
+                        returns[mb_idx], cfg.ppo_clip, cfg.value_loss_weight, cfg.entropy_beta,
+                        False)
                     if record is not None:
-                        record.append(torch.stack([loss, l_pi, l_v, dist.entropy().mean()]).detach())
+                        record.append(torch.stack([loss, l_pi, l_v, ent]).detach())
                     if world > 1:
                         # local mean x 1/world, summed over the ranks = the union minibatch's mean
                         loss = loss * (1.0 / world)
@@ -533,10 +525,7 @@ class RecurrentPPO:
                 if world > 1:
                     torch.distributed.all_reduce(self.flat.grad)
                 step += 1
-                N.check(lib.dppo_clip_adam_f32(
-                    self.flat.flat.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(),
-                    self.v.data_ptr(), self.flat.total, cfg.grad_norm_clip, float(lr), 0.9, 0.999,
-                    cfg.adam_eps, step, None, stream), "dppo_clip_adam_f32")
+                clip_adam(self.flat, self.m, self.v, cfg, lr, step, stream)
         self.core_scan_calls += CORE_SCAN_CALLS[0] - scans0
         if record is not None:
             self.last_losses = torch.stack(record)
@@ -558,11 +547,7 @@ class RecurrentPPO:
         hx0 = f32(hx.reshape(cfg.num_envs, cfg.gru_hidden_dim))
         batch = N.GruBatch(obs.data_ptr(), act.data_ptr(), old_lp.data_ptr(), adv.data_ptr(),
                            ret.data_ptr(), dones.data_ptr(), hx0.data_ptr())
-        hp = N.HParams(gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, ppo_clip=cfg.ppo_clip,
-                       value_loss_weight=cfg.value_loss_weight, entropy_beta=cfg.entropy_beta,
-                       grad_norm_clip=cfg.grad_norm_clip, adam_beta1=0.9, adam_beta2=0.999,
-                       adam_eps=cfg.adam_eps, advantage_norm=int(bool(cfg.advantage_norm)),
-                       lr=float(lr), adam_step=int(step))
+        hp = hparams(cfg, lr, step)
         idx32 = idx.to(torch.int32).contiguous()
         mb = idx32.shape[-1]
         m_total = mb * world          # the union minibatch's size under data parallelism
@@ -579,10 +564,7 @@ class RecurrentPPO:
                     torch.distributed.all_reduce(self.flat.grad)
                 losses.append(self.flat.grad[total:total + 3].clone())
                 step += 1
-                N.check(lib.dppo_clip_adam_f32(
-                    self.flat.flat.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(),
-                    self.v.data_ptr(), total, cfg.grad_norm_clip, float(lr), 0.9, 0.999,
-                    cfg.adam_eps, step, None, stream), "dppo_clip_adam_f32")
+                clip_adam(self.flat, self.m, self.v, cfg, lr, step, stream)
         # {loss, policy, value, entropy} per minibatch (reference never logs these; for tests)
         sums = torch.stack(losses) / float(m_total)
         self.last_losses = torch.stack([sums[:, 0] + cfg.value_loss_weight * sums[:, 1]
