@@ -43,10 +43,12 @@ int gru_validate(const dppo_gru_dims* d) {
     set_error("invalid dppo_gru_dims");
     return DPPO_EINVAL;
   }
-  if (d->hidden != kH || !gru_width_ok(d->gru_hidden) || d->obs_dim > 32 || d->act_dim > kAPad) {
-    set_error("fused GRU kernels support hidden=64, gru_hidden in {16, 32, 64}, obs_dim<=32, "
-              "act_dim<=16 "
-              "(got H=%d G=%d D=%d A=%d)", d->hidden, d->gru_hidden, d->obs_dim, d->act_dim);
+  if (d->hidden != kH || !gru_width_ok(d->gru_hidden) || d->obs_dim > (d->wide_obs ? 128 : 32) ||
+      d->act_dim > kAPad) {
+    set_error("fused GRU kernels support hidden=64, gru_hidden in {16, 32, 64}, obs_dim<=32 "
+              "(<=128 with wide_obs), act_dim<=16 "
+              "(got H=%d G=%d D=%d A=%d wide_obs=%d)", d->hidden, d->gru_hidden, d->obs_dim,
+              d->act_dim, d->wide_obs);
     return DPPO_EUNSUPPORTED;
   }
   if ((int64_t)d->rollout_steps * d->num_envs > 0x7FFFFFFF / (4 * d->gru_hidden)) {

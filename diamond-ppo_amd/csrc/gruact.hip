@@ -3,7 +3,9 @@
 // oracle/gru_torch.py::sequence): what rollout() ran under torch as several dozen launches per env
 // step is one launch for the policy step (gru_act_kernel: base, GRU cell, both heads, Categorical
 // draw, log-prob) and one for V(next_obs) (gru_value_kernel: base, GRU cell, critic head).  Both
-// kernels are templates on the GRU hidden width G, instantiated for 16, 32 and 64.
+// kernels are templates on the GRU hidden width G, instantiated for 16, 32 and 64, and on the
+// per-env observation capacity of their LDS: 32 floats, or 128 for the observations of 33 to 128
+// floats that dppo_gru_dims.wide_obs admits (another 384 B per env, nothing else differs).
 //
 // Mapping: G lanes per env (lane j = hidden unit j, grugrad.hip's phase-B mapping), 4 envs per
 // workgroup (4 G threads: one wave at G = 16, 2 at G = 32, 4 at G = 64); an env never straddles a
@@ -45,10 +47,10 @@ struct GruStepArgs {
   uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
 };
 
-// per-env LDS vectors (floats)
-template <int G>
+// per-env LDS vectors (floats); OBS = the observation capacity, 32 or (wide_obs) 128
+template <int G, int OBS>
 struct EnvLds {
-  float obs[32];
+  float obs[OBS];
   float x1[kH];
   float h[G];
   float ya[kH];
@@ -97,8 +99,8 @@ __device__ __forceinline__ void head_hidden(const float* __restrict__ W1,
 // Base layer, hidden reset and one GRU step for one env slot of the workgroup; on return E.h
 // holds the new hidden state (all G lanes of the env see it) and the return value is lane j's own
 // element.
-template <int G>
-__device__ __forceinline__ float gru_forward(const GruStepArgs& a, EnvLds<G>& E, int64_t ic,
+template <int G, int OBS>
+__device__ __forceinline__ float gru_forward(const GruStepArgs& a, EnvLds<G, OBS>& E, int64_t ic,
                                              int j) {
   constexpr int Q = kH / G;
   const float* P = a.params;
@@ -153,8 +155,9 @@ __device__ __forceinline__ float gru_forward(const GruStepArgs& a, EnvLds<G>& E,
 }
 
 // critic head on E.h: Linear(G, 64) tanh Linear(64, 1)
-template <int G>
-__device__ __forceinline__ float critic_value(const GruStepArgs& a, const EnvLds<G>& E, int j) {
+template <int G, int OBS>
+__device__ __forceinline__ float critic_value(const GruStepArgs& a, const EnvLds<G, OBS>& E,
+                                              int j) {
   const float* P = a.params;
   float yc[kH / G];
   head_hidden<G>(P + a.po.Wc1, P + a.po.bc1, E.h, j, yc);
@@ -164,20 +167,20 @@ __device__ __forceinline__ float critic_value(const GruStepArgs& a, const EnvLds
   return P[a.po.bc2] + env_sum<G>(part);
 }
 
-template <int G>
+template <int G, int OBS = 32>
 __global__ __launch_bounds__(kEnvsPerWg* G) void gru_act_kernel(GruStepArgs a) {
-  __shared__ __attribute__((aligned(16))) EnvLds<G> lds[kEnvsPerWg];
+  __shared__ __attribute__((aligned(16))) EnvLds<G, OBS> lds[kEnvsPerWg];
   const int e = threadIdx.x / G, j = threadIdx.x % G;
   const int64_t i = (int64_t)blockIdx.x * kEnvsPerWg + e;
   const bool valid = i < a.n;
   const int64_t ic = valid ? i : a.n - 1;
-  EnvLds<G>& E = lds[e];
+  EnvLds<G, OBS>& E = lds[e];
   const float* P = a.params;
   const int A = a.A;
 
-  const float hn = gru_forward<G>(a, E, ic, j);
+  const float hn = gru_forward<G, OBS>(a, E, ic, j);
   if (valid) a.hx_out[i * G + j] = hn;
-  const float value = critic_value<G>(a, E, j);
+  const float value = critic_value<G, OBS>(a, E, j);
 
   // actor head: Linear(G, 64) tanh Linear(64, A); lane k < A computes logit k
   float ya[kH / G];
@@ -239,15 +242,15 @@ __global__ __launch_bounds__(kEnvsPerWg* G) void gru_act_kernel(GruStepArgs a) {
   a.values[i] = value;
 }
 
-template <int G>
+template <int G, int OBS = 32>
 __global__ __launch_bounds__(kEnvsPerWg* G) void gru_value_kernel(GruStepArgs a) {
-  __shared__ __attribute__((aligned(16))) EnvLds<G> lds[kEnvsPerWg];
+  __shared__ __attribute__((aligned(16))) EnvLds<G, OBS> lds[kEnvsPerWg];
   const int e = threadIdx.x / G, j = threadIdx.x % G;
   const int64_t i = (int64_t)blockIdx.x * kEnvsPerWg + e;
   const bool valid = i < a.n;
-  EnvLds<G>& E = lds[e];
-  gru_forward<G>(a, E, valid ? i : a.n - 1, j);
-  const float value = critic_value<G>(a, E, j);
+  EnvLds<G, OBS>& E = lds[e];
+  gru_forward<G, OBS>(a, E, valid ? i : a.n - 1, j);
+  const float value = critic_value<G, OBS>(a, E, j);
   if (valid && j == 0) a.values[i] = value;
 }
 
@@ -261,12 +264,21 @@ int grid_for_envs(int64_t n, unsigned* grid) {
   return DPPO_OK;
 }
 
+constexpr int kWideObs = 128;  // observation capacity of the wide_obs instantiations
+
 template <int G>
 void launch_width(bool act, unsigned grid, const GruStepArgs& a, hipStream_t s) {
-  if (act)
-    DPPO_LAUNCH(gru_act_kernel<G>, dim3(grid), dim3(kEnvsPerWg * G), 0, s, a);
-  else
-    DPPO_LAUNCH(gru_value_kernel<G>, dim3(grid), dim3(kEnvsPerWg * G), 0, s, a);
+  const dim3 block(kEnvsPerWg * G);
+  if (a.D > 32) {
+    if (act)
+      DPPO_LAUNCH((gru_act_kernel<G, kWideObs>), dim3(grid), block, 0, s, a);
+    else
+      DPPO_LAUNCH((gru_value_kernel<G, kWideObs>), dim3(grid), block, 0, s, a);
+  } else if (act) {
+    DPPO_LAUNCH(gru_act_kernel<G>, dim3(grid), block, 0, s, a);
+  } else {
+    DPPO_LAUNCH(gru_value_kernel<G>, dim3(grid), block, 0, s, a);
+  }
 }
 
 // The one fill of the kernel arguments and the one dispatch on G: the policy step (act) or the

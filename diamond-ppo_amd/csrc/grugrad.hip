@@ -28,6 +28,9 @@
 //     v_mfma_f32_16x16x4_f32 (k = sample) in a fixed order, bias sums on VALU, one slab per
 //     workgroup (optim.hip's slab reduction sums them in a fixed order: bit-reproducible).
 // No per-thread array is ever indexed by a run-time value (that would put it in scratch memory).
+// gru_grad_kernel<G, true> is the form for observations of 33 to 128 floats: phase A's base layer
+// walks the observation row in blocks of 32 columns (base8_wide); everything else is the same
+// code, already written in D and D16.
 //
 // LDS holds the biases for the whole launch and, in one region restaged between the phases' own
 // barriers, only the weights the current phase reads: A Wb + Wih | B, D Whh | C Wa1 Wc1 Wa2 |
@@ -152,7 +155,57 @@ __device__ __forceinline__ f32x4 tile_sum(const float* __restrict__ A, int lda, 
   return acc;
 }
 
-template <int G>
+// Phase A's base layer at 33 <= D <= 128, eight features of one sample:
+// z[u] = bb[u] + sum_c Wb8[u][c] ob[c], c ascending as at D <= 32.  The observation row is
+// re-read from the sample's scratch copy ob16 (D16 floats, zeros from D on, 16-byte aligned) 32
+// columns at a time, so the registers that hold it are indexed at compile time only; the block
+// that holds column D - 1, where it is not a full one, checks c < D.  Wb8: rows of D floats in LDS.
+__device__ __forceinline__ void base8_wide(float (&z)[8], const float* bb, const float* Wb8, int D,
+                                           int D16, const float* ob16) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) z[u] = bb[u];
+  int c0 = 0;
+#pragma unroll 1
+  for (; c0 + 32 <= D; c0 += 32) {
+    float ob[32];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const f32x4 v = *(const f32x4*)(ob16 + c0 + 4 * q);
+      ob[4 * q] = v[0];
+      ob[4 * q + 1] = v[1];
+      ob[4 * q + 2] = v[2];
+      ob[4 * q + 3] = v[3];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+#pragma unroll
+      for (int k = 0; k < 32; ++k) z[u] += Wb8[u * D + c0 + k] * ob[k];
+    }
+  }
+  if (c0 < D) {
+    float ob[32];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (c0 + 4 * q < D16) v = *(const f32x4*)(ob16 + c0 + 4 * q);
+      ob[4 * q] = v[0];
+      ob[4 * q + 1] = v[1];
+      ob[4 * q + 2] = v[2];
+      ob[4 * q + 3] = v[3];
+    }
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      if (c0 + k < D) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) z[u] += Wb8[u * D + c0 + k] * ob[k];
+      }
+    }
+  }
+}
+
+// WIDE_OBS: the form for 33 <= D <= 128 (dppo_gru_dims.wide_obs); phase A's base layer alone
+// differs.
+template <int G, bool WIDE_OBS = false>
 __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
   constexpr int kEnvs = kThr / G, G3 = 3 * G;
   static_assert(G3 % kGiBlk == 0 && G3 <= kThr && G % 16 == 0, "gate blocking");
@@ -199,13 +252,24 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
     const int t = s / ne, e = s - t * ne;
     const int64_t i = (int64_t)t * N + n0 + e;
     {
-      float ob[32];
-#pragma unroll
-      for (int c = 0; c < 32; ++c) ob[c] = c < D ? a.b.obs[i * D + c] : 0.f;
+      [[maybe_unused]] float ob[32];
       float* ob16 = sc.obs + i * a.D16;
+      if constexpr (WIDE_OBS) {
+        // the row goes to its D16-wide scratch row first; base8_wide re-reads it from there
+#pragma unroll 1
+        for (int c = 0; c < a.D16; c += 4) {
+          f32x4 v;
 #pragma unroll
-      for (int c = 0; c < 32; ++c)
-        if (c < a.D16) ob16[c] = ob[c];
+          for (int k = 0; k < 4; ++k) v[k] = c + k < D ? a.b.obs[i * D + c + k] : 0.f;
+          *(f32x4*)(ob16 + c) = v;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 32; ++c) ob[c] = c < D ? a.b.obs[i * D + c] : 0.f;
+#pragma unroll
+        for (int c = 0; c < 32; ++c)
+          if (c < a.D16) ob16[c] = ob[c];
+      }
       [[maybe_unused]] float gi[kOneBlk ? kGiBlk : 1];
       if constexpr (kOneBlk) {
 #pragma unroll
@@ -214,12 +278,18 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
 #pragma unroll 1
       for (int o0 = 0; o0 < kH; o0 += 8) {
         float x[8];
+        if constexpr (WIDE_OBS) base8_wide(x, lds + L.bb + o0, Wb + o0 * D, D, a.D16, ob16);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          float z = lds[L.bb + o0 + u];
+          float z;
+          if constexpr (WIDE_OBS) {
+            z = x[u];
+          } else {
+            z = lds[L.bb + o0 + u];
 #pragma unroll
-          for (int c = 0; c < 32; ++c)
-            if (c < D) z += Wb[(o0 + u) * D + c] * ob[c];
+            for (int c = 0; c < 32; ++c)
+              if (c < D) z += Wb[(o0 + u) * D + c] * ob[c];
+          }
           x[u] = tanh_acc(z);
         }
         f32x4* xo = (f32x4*)(sc.x1 + i * kH + o0);
@@ -591,10 +661,15 @@ template <int G>
 int launch_g(const GruArgs& a, hipStream_t s) {
   static const bool attr = [] {
     raise_dyn_lds((const void*)gru_grad_kernel<G>);
+    raise_dyn_lds((const void*)gru_grad_kernel<G, true>);
     return true;
   }();
   (void)attr;
-  DPPO_LAUNCH(gru_grad_kernel<G>, dim3(gru_grid(a.N, G)), dim3(kThr), gru_lds_bytes(a.D, G), s, a);
+  const dim3 grid(gru_grid(a.N, G));
+  if (a.D > 32)
+    DPPO_LAUNCH((gru_grad_kernel<G, true>), grid, dim3(kThr), gru_lds_bytes(a.D, G), s, a);
+  else
+    DPPO_LAUNCH(gru_grad_kernel<G>, grid, dim3(kThr), gru_lds_bytes(a.D, G), s, a);
   DPPO_LAUNCH_CHECK();
   return DPPO_OK;
 }

@@ -77,7 +77,8 @@ class Layout(ctypes.Structure):
 class GruDims(ctypes.Structure):
     _fields_ = [("rollout_steps", ctypes.c_int32), ("num_envs", ctypes.c_int32),
                 ("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32),
-                ("hidden", ctypes.c_int32), ("gru_hidden", ctypes.c_int32)]
+                ("hidden", ctypes.c_int32), ("gru_hidden", ctypes.c_int32),
+                ("wide_obs", ctypes.c_int32)]   # 0 (the default): obs_dim <= 32; else <= 128
 
 
 class GruBatch(ctypes.Structure):

@@ -65,6 +65,9 @@ class RecurrentPPOConfig:
     verbose: bool = True
     device_index: int = 0
     gae_bitexact: bool = True   # False: the chunked affine-scan GAE kernel (PPOConfig)
+    # True: the fused kernels (fused_gru, fused_rollout) also serve observations of 33 to 128
+    # floats (fused_gru_shape's wide_obs); up to 32 nothing changes, bits included
+    wide_observations: bool = False
 
 
 CORE_SCAN_CALLS = [0]  # GRUCore forwards of this process that the scan kernels served
@@ -230,12 +233,14 @@ def network_parameter_init_(network: nn.Module, gain: float = 1.0) -> None:
             nn.init.orthogonal_(network.actor_out_layer.weight, gain=0.01)
 
 
-def fused_gru_shape(hidden: int, gru_hidden: int, obs_dim: int, act_dim: int) -> bool:
+def fused_gru_shape(hidden: int, gru_hidden: int, obs_dim: int, act_dim: int,
+                    wide_obs: bool = False) -> bool:
     """Whether the fused GRU kernels (``fused_gru``, ``fused_rollout``) serve the default network
-    at this shape: hidden 64, gru_hidden 16, 32 or 64, obs_dim <= 32, act_dim <= 16.  The same
-    predicate as ``gru_validate`` (csrc/gru.hip).  ``DPPO_GRU_WIDE=0`` turns gru_hidden 32 and 64
-    off (A/B runs against the torch path); 16 is not affected."""
-    if not (hidden == 64 and 1 <= obs_dim <= 32 and 1 <= act_dim <= 16):
+    at this shape: hidden 64, gru_hidden 16, 32 or 64, act_dim <= 16 and obs_dim <= 32, or
+    <= 128 with ``wide_obs`` (``RecurrentPPOConfig.wide_observations``, ``dppo_gru_dims.wide_obs``).
+    The same predicate as ``gru_validate`` (csrc/gru.hip).  ``DPPO_GRU_WIDE=0`` turns gru_hidden
+    32 and 64 off (A/B runs against the torch path); 16 is not affected."""
+    if not (hidden == 64 and 1 <= obs_dim <= (128 if wide_obs else 32) and 1 <= act_dim <= 16):
         return False
     if gru_hidden == 16:
         return True
@@ -289,12 +294,13 @@ class RecurrentPPO:
         self.handle = N.Handle(self.device.index or 0, dims)
         self.gru = None
         obs_dim = int(np.prod(obs_space.shape))
+        wide_obs = bool(getattr(cfg, "wide_observations", False))
         if (type(self.network) is RecurrentActorCriticNetwork
                 and fused_gru_shape(cfg.network_hidden_dim, cfg.gru_hidden_dim, obs_dim,
-                                    int(act_space.n))):
+                                    int(act_space.n), wide_obs)):
             gd = N.GruDims(rollout_steps=cfg.rollout_steps, num_envs=cfg.num_envs,
                            obs_dim=obs_dim, act_dim=int(act_space.n), hidden=64,
-                           gru_hidden=cfg.gru_hidden_dim)
+                           gru_hidden=cfg.gru_hidden_dim, wide_obs=int(wide_obs))
             self.gru = N.GruHandle(self.device.index or 0, gd)
             L = self.gru.layout
             if L.total != self.flat.total or any(L.offset[i] != o for i, o in

@@ -443,10 +443,13 @@ typedef struct dppo_gru_handle dppo_gru_handle;
 typedef struct dppo_gru_dims {
   int32_t rollout_steps; /* T */
   int32_t num_envs;      /* N */
-  int32_t obs_dim;       /* D <= 32 */
+  int32_t obs_dim;       /* D <= 32, or <= 128 with wide_obs */
   int32_t act_dim;       /* discrete actions A <= 16 */
   int32_t hidden;        /* network_hidden_dim, must be 64 */
   int32_t gru_hidden;    /* gru_hidden_dim G: 16, 32 or 64 */
+  int32_t wide_obs;      /* 0: obs_dim <= 32.  Non-zero: obs_dim <= 128; shapes of 33 to 128 run
+                            the wide-observation instantiations of the three kernels, obs_dim <= 32
+                            runs the same kernels and gives the same bits as with 0 */
 } dppo_gru_dims;
 
 /* One rollout as RecurrentPPO.learn stacks it (recurrent_ppo.py:306-316), device pointers. */
@@ -463,12 +466,16 @@ typedef struct dppo_gru_batch {
 /* Flat parameter layout of RecurrentActorCriticNetwork (named_parameters() order, 16-float
  * aligned offsets; 14 tensors). */
 int dppo_gru_param_layout(const dppo_gru_dims* dims, dppo_layout* out);
+/* DPPO_EUNSUPPORTED outside hidden 64, gru_hidden 16 / 32 / 64, act_dim <= 16 and obs_dim <= 32
+ * (dims->wide_obs 0) or <= 128 (non-zero).  The workspace's per-sample scratch row grows with
+ * obs_dim rounded up to 16. */
 int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out);
 void dppo_gru_destroy(dppo_gru_handle* h);
 /* How the kernels map a supported shape (no device needed): out[0] envs per workgroup of the
  * minibatch kernel, out[1] its workgroups (= gradient slabs) for dims->num_envs, out[2] its LDS
- * bytes, out[3] envs per workgroup of the two rollout kernels.  DPPO_EUNSUPPORTED as
- * dppo_gru_create. */
+ * bytes at this obs_dim and gru_hidden (about 90 KB at obs_dim 128, gru_hidden 64, under
+ * wide_obs), out[3] envs per workgroup of the two rollout kernels.  DPPO_EUNSUPPORTED as
+ * dppo_gru_create, wide_obs included. */
 int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out);
 
 /* One minibatch gradient of the recurrent PPO loss (recurrent_ppo.py:335-360): the GRU sequence

@@ -13,6 +13,16 @@ two medians lie inside each other's min-max spread (then neither path is ahead).
 
 All three widths run gru_grad_kernel<G> (csrc/grugrad.hip).  With `fused_gru` off an agent runs exactly what it ran before the fused
 kernel existed for its G.
+
+`--obs-dim D --act-dim A` set the observation width and the action count.  Past 32 observations
+the fused kernels are asked for with `--wide-observations` (RecurrentPPOConfig.wide_observations),
+and the yardstick is the same shape without the flag, which runs what it always ran, the torch
+loop: three agents then alternate, `fused` (flag on), `torch` (flag off) and `torch_core` (flag
+off, `fused_core` on: GRUCore on the scan kernels), and each row says whether the fused path's
+slowest learn is below the other's fastest:
+
+    python tools/bench_recurrent_learn.py --obs-dim 128 --act-dim 6 --wide-observations \
+        --sizes 32 8192 --out bench_out/recurrent_wide_obs_learn.json
 """
 import argparse
 import json
@@ -32,24 +42,27 @@ import torch
 import diamond
 import gym_stub
 
-T, D, A = 32, 8, 4
+T, D, A = 32, 8, 4      # D, A: the defaults of --obs-dim / --act-dim
 SIZES = [32, 1024, 8192]
 WIDTHS = [16, 32, 64]
 
 
-def make_agent(Nn, G, fused):
+def make_agent(Nn, G, fused, D=D, A=A, wide_obs=False, core=False):
+    """fused: the minibatch kernel (with wide_obs: asked for through the config flag).  Not fused:
+    the torch loop, by fused_gru = False or, where wide_obs is tested, by leaving the flag off."""
     np.random.seed(0)
     torch.manual_seed(0)
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
     cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
-                                     gru_hidden_dim=G)
+                                     gru_hidden_dim=G, wide_observations=wide_obs and fused)
     agent = diamond.RecurrentPPO(None, cfg, envs=envs)
-    assert agent.gru is not None
+    assert (agent.gru is not None) == (fused or not wide_obs)
     agent.fused_gru = fused
+    agent.fused_core = core
     return agent
 
 
-def experience(Nn, G, device, seed=0):
+def experience(Nn, G, device, seed=0, D=D, A=A):
     """One rollout in RecurrentPPO.rollout()'s layout, random contents."""
     rng = np.random.default_rng(seed)
     g = lambda x, dt=torch.float32: torch.as_tensor(x, dtype=dt, device=device)
@@ -68,9 +81,12 @@ def timed_learn(agent, exp):
     return (time.perf_counter() - t0) * 1e3
 
 
-def run(Nn, G, warmup, learns):
-    agents = {"fused": make_agent(Nn, G, True), "torch": make_agent(Nn, G, False)}
-    exp = experience(Nn, G, agents["fused"].device)
+def run(Nn, G, warmup, learns, D=D, A=A, wide_obs=False):
+    agents = {"fused": make_agent(Nn, G, True, D, A, wide_obs),
+              "torch": make_agent(Nn, G, False, D, A, wide_obs)}
+    if wide_obs:
+        agents["torch_core"] = make_agent(Nn, G, False, D, A, wide_obs, core=True)
+    exp = experience(Nn, G, agents["fused"].device, D=D, A=A)
     ms = {k: [] for k in agents}
     for r in range(warmup + learns):
         for k, agent in agents.items():
@@ -87,6 +103,11 @@ def run(Nn, G, warmup, learns):
     out["fused_is_slower"] = out["torch_over_fused"] < 1.0
     inside = lambda a, b: out[b + "_ms_min"] <= out[a + "_ms_median"] <= out[b + "_ms_max"]
     out["medians_inside_each_others_spread"] = inside("fused", "torch") and inside("torch", "fused")
+    if wide_obs:
+        out["wide_observations"] = True
+        out["torch_core_over_fused"] = out["torch_core_ms_median"] / out["fused_ms_median"]
+        for k in ("torch", "torch_core"):
+            out[f"fused_max_below_{k}_min"] = out["fused_ms_max"] < out[k + "_ms_min"]
     return out
 
 
@@ -97,11 +118,14 @@ def main():
     ap.add_argument("--learns", type=int, default=20)
     ap.add_argument("--gru-hidden", type=int, nargs="+", default=WIDTHS)
     ap.add_argument("--sizes", type=int, nargs="+", default=SIZES)
+    ap.add_argument("--obs-dim", type=int, default=D)
+    ap.add_argument("--act-dim", type=int, default=A)
+    ap.add_argument("--wide-observations", action="store_true")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "rows": []}
     for G in a.gru_hidden:
         for Nn in a.sizes:
-            r = run(Nn, G, a.warmup, a.learns)
+            r = run(Nn, G, a.warmup, a.learns, a.obs_dim, a.act_dim, a.wide_observations)
             print(json.dumps(r), flush=True)
             res["rows"].append(r)
     if a.out:

@@ -17,6 +17,15 @@ csrc/gruact.hip's kernels at G = 32 / 64, and a result row of a width other than
 
 In a separate pass (events on every launch slow the host) the library's timing mode
 (dppo_gru_set_timing) gives the two kernels' own execution time per launch.
+
+`--obs-dim D --act-dim A --sizes N [N ...]` set the shape.  Past 32 observations the fused
+kernels are asked for with `--wide-observations` (RecurrentPPOConfig.wide_observations); the
+yardstick is the same shape without the flag, the torch rollout it always ran, without and with
+`fused_core` (`torch_core`), and each row says whether the fused path's slowest rollout is below
+the other's fastest:
+
+    python tools/bench_recurrent_rollout.py --gru-hidden 16 32 64 --obs-dim 128 --act-dim 6 \
+        --wide-observations --sizes 32 8192 --out bench_out/recurrent_wide_obs_rollout.json
 """
 import argparse
 import json
@@ -36,19 +45,22 @@ import torch
 import diamond
 import gym_stub
 
-T, D, A = 32, 8, 4
+T, D, A = 32, 8, 4      # D, A: the defaults of --obs-dim / --act-dim
 SIZES = [32, 1024, 8192]
 
 
-def make_agent(Nn, fused, G=16):
+def make_agent(Nn, fused, G=16, D=D, A=A, wide_obs=False, core=False):
+    """fused: the step kernels (with wide_obs: asked for through the config flag).  Not fused:
+    the torch rollout; where wide_obs is tested the flag stays off, so no fused path exists."""
     np.random.seed(0)
     torch.manual_seed(0)
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
     cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
-                                     gru_hidden_dim=G)
+                                     gru_hidden_dim=G, wide_observations=wide_obs and fused)
     agent = diamond.RecurrentPPO(None, cfg, envs=envs)
-    assert agent.gru is not None
+    assert (agent.gru is not None) == (fused or not wide_obs)
     agent.fused_rollout = fused
+    agent.fused_core = core
     agent.current_observations, _ = agent.envs.reset(seed=1)
     agent.prev_dones = np.zeros(Nn, dtype=bool)
     agent.current_hx = torch.zeros(1, Nn, cfg.gru_hidden_dim, device=agent.device)
@@ -63,8 +75,11 @@ def timed_rollout(agent):
     return (time.perf_counter() - t0) * 1e3
 
 
-def run(Nn, warmup, rollouts, kernel_rollouts, G=16):
-    agents = {"fused": make_agent(Nn, True, G), "torch": make_agent(Nn, False, G)}
+def run(Nn, warmup, rollouts, kernel_rollouts, G=16, D=D, A=A, wide_obs=False):
+    agents = {"fused": make_agent(Nn, True, G, D, A, wide_obs),
+              "torch": make_agent(Nn, False, G, D, A, wide_obs)}
+    if wide_obs:
+        agents["torch_core"] = make_agent(Nn, False, G, D, A, wide_obs, core=True)
     ms = {k: [] for k in agents}
     for r in range(warmup + rollouts):
         for k, agent in agents.items():
@@ -79,6 +94,11 @@ def run(Nn, warmup, rollouts, kernel_rollouts, G=16):
         out[k + "_ms_min"], out[k + "_ms_max"] = min(v), max(v)
     out["torch_over_fused"] = out["torch_ms_median"] / out["fused_ms_median"]
     out["fused_is_slower"] = out["torch_over_fused"] < 1.0
+    if wide_obs:
+        out["wide_observations"] = True
+        out["torch_core_over_fused"] = out["torch_core_ms_median"] / out["fused_ms_median"]
+        for k in ("torch", "torch_core"):
+            out[f"fused_max_below_{k}_min"] = out["fused_ms_max"] < out[k + "_ms_min"]
     gru = agents["fused"].gru
     gru.set_timing(True)
     for _ in range(kernel_rollouts):
@@ -98,11 +118,16 @@ def main():
     ap.add_argument("--rollouts", type=int, default=20)
     ap.add_argument("--kernel-rollouts", type=int, default=5)
     ap.add_argument("--gru-hidden", type=int, nargs="+", default=[16])
+    ap.add_argument("--sizes", type=int, nargs="+", default=SIZES)
+    ap.add_argument("--obs-dim", type=int, default=D)
+    ap.add_argument("--act-dim", type=int, default=A)
+    ap.add_argument("--wide-observations", action="store_true")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "sizes": []}
     for G in a.gru_hidden:
-        for Nn in SIZES:
-            r = run(Nn, a.warmup, a.rollouts, a.kernel_rollouts, G)
+        for Nn in a.sizes:
+            r = run(Nn, a.warmup, a.rollouts, a.kernel_rollouts, G, a.obs_dim, a.act_dim,
+                    a.wide_observations)
             print(json.dumps(r), flush=True)
             res["sizes"].append(r)
     if a.out:
