@@ -496,6 +496,14 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
                     const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
                     int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
                     float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s);
+// The Gaussian head (gru_grad_kernel<G, WIDE_OBS, true>): b.actions float [T][N][A], log_std at
+// ls_off of the flat layout, dls [B][16] its per-sample gradient rows; 128 B more LDS.
+size_t gru_gauss_lds_bytes(int D, int G);
+int launch_gru_gauss_grad(int G, const GruOffsets& po, int64_t ls_off, const float* params,
+                          const dppo_gru_gauss_batch& b, const int32_t* idx, int32_t m,
+                          float* wmask, int64_t B, int T, int N, int D, int A, float inv_m,
+                          float clip_eps, float vf, float ent, const GruScratch& sc, float* dls,
+                          float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s);
 
 // The GRU kernels' gate non-linearities (grugrad.hip learn, gruact.hip rollout: the same bits)
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
@@ -511,6 +519,11 @@ __device__ __forceinline__ float tanh_acc(float x) {
 int gru_act_envs();  // envs per workgroup
 int launch_gru_act(int G, const GruOffsets& po, const float* params, const dppo_gru_step& st,
                    int64_t n, int D, int A, uint64_t seed, uint64_t counter, hipStream_t s);
+// The Gaussian policy step: means in place of logits, draw_gaussian (actdraw.h) in place of the
+// Categorical draw, the log-prob from the stored float32 action.
+int launch_gru_gauss_act(int G, const GruOffsets& po, int64_t ls_off, const float* params,
+                         const dppo_gru_gauss_step& st, int64_t n, int D, int A, uint64_t seed,
+                         uint64_t counter, hipStream_t s);
 int launch_gru_value(int G, const GruOffsets& po, const float* params, const float* obs,
                      const float* hx, const uint8_t* dones, int64_t n, int D, float* values,
                      hipStream_t s);

@@ -13,6 +13,9 @@ using namespace dppo;
 
 struct dppo_gru_handle {
   int device = 0;
+  bool gauss = false;     // the Gaussian head's layout and kernels (dppo_gru_gauss_create)
+  int64_t ls_off = 0;     // actor_log_std in the Gaussian layout
+  float* dls = nullptr;   // [B][16] per-sample log_std gradient rows (Gaussian)
   dppo_gru_dims dims{};
   dppo_layout layout{};
   GruOffsets po{};
@@ -58,25 +61,66 @@ int gru_validate(const dppo_gru_dims* d) {
   return DPPO_OK;
 }
 
-void gru_layout(const dppo_gru_dims* d, dppo_layout* L) {
+// gauss: RecurrentContinuousActorCriticNetwork's 15 tensors, actor_log_std [1][A] first
+// (diamond/recurrent_continuous_ppo.py), then the same 14.
+void gru_layout(const dppo_gru_dims* d, dppo_layout* L, bool gauss = false) {
   std::memset(L, 0, sizeof(*L));
   const int D = d->obs_dim, A = d->act_dim, G = d->gru_hidden;
   // RecurrentActorCriticNetwork.named_parameters() order (diamond/recurrent_ppo.py)
   const int rc[14][2] = {{kH, D}, {kH, 1}, {3 * G, kH}, {3 * G, G}, {3 * G, 1}, {3 * G, 1},
                          {kH, G}, {kH, 1}, {A, kH}, {A, 1}, {kH, G}, {kH, 1}, {1, kH}, {1, 1}};
   int64_t off = 0, real = 0;
-  for (int i = 0; i < 14; ++i) {
-    const int64_t ne = (int64_t)rc[i][0] * rc[i][1];
-    L->offset[i] = off;
-    L->numel[i] = ne;
-    L->rows[i] = rc[i][0];
-    L->cols[i] = rc[i][1];
+  int c = 0;
+  auto put = [&](int rows, int cols) {
+    const int64_t ne = (int64_t)rows * cols;
+    L->offset[c] = off;
+    L->numel[c] = ne;
+    L->rows[c] = rows;
+    L->cols[c] = cols;
     off = (off + ne + 15) / 16 * 16;
     real += ne;
-  }
-  L->count = 14;
+    ++c;
+  };
+  if (gauss) put(1, A);
+  for (int i = 0; i < 14; ++i) put(rc[i][0], rc[i][1]);
+  L->count = c;
   L->total = off;
   L->n_real = real;
+}
+
+int gru_layout_checked(const dppo_gru_dims* dims, dppo_layout* out, bool gauss) {
+  if (!out) {
+    set_error("out is NULL");
+    return DPPO_EINVAL;
+  }
+  const int rc = gru_validate(dims);
+  if (rc != DPPO_OK && rc != DPPO_EUNSUPPORTED) return rc;
+  gru_layout(dims, out, gauss);
+  return DPPO_OK;
+}
+
+int gru_plan(const dppo_gru_dims* dims, int32_t* out, bool gauss) {
+  if (!out) {
+    set_error("out is NULL");
+    return DPPO_EINVAL;
+  }
+  const int rc = gru_validate(dims);
+  if (rc != DPPO_OK) return rc;
+  const int G = dims->gru_hidden;
+  out[0] = gru_envs(G);
+  out[1] = gru_grid(dims->num_envs, G);
+  out[2] = (int32_t)(gauss ? gru_gauss_lds_bytes(dims->obs_dim, G)
+                           : gru_lds_bytes(dims->obs_dim, G));
+  out[3] = gru_act_envs();
+  return DPPO_OK;
+}
+
+// A launch that belongs to the other head kind: DPPO_EINVAL, nothing launched.
+int gru_kind_check(const dppo_gru_handle* h, bool gauss, const char* fn) {
+  if (h->gauss == gauss) return DPPO_OK;
+  set_error("%s: the handle was created for the %s head", fn,
+            h->gauss ? "Gaussian (dppo_gru_gauss_create)" : "categorical (dppo_gru_create)");
+  return DPPO_EINVAL;
 }
 
 // Hands the next launch of this thread an event pair of its own when the handle's timing is on
@@ -108,14 +152,11 @@ struct GruTimed {
 extern "C" {
 
 int dppo_gru_param_layout(const dppo_gru_dims* dims, dppo_layout* out) {
-  if (!out) {
-    set_error("out is NULL");
-    return DPPO_EINVAL;
-  }
-  const int rc = gru_validate(dims);
-  if (rc != DPPO_OK && rc != DPPO_EUNSUPPORTED) return rc;
-  gru_layout(dims, out);
-  return DPPO_OK;
+  return gru_layout_checked(dims, out, false);
+}
+
+int dppo_gru_gauss_param_layout(const dppo_gru_dims* dims, dppo_layout* out) {
+  return gru_layout_checked(dims, out, true);
 }
 
 void dppo_gru_destroy(dppo_gru_handle* h) {
@@ -126,11 +167,16 @@ void dppo_gru_destroy(dppo_gru_handle* h) {
   (void)hipFree(h->wmask);
   (void)hipFree(h->slabs);
   (void)hipFree(h->sq_part);
+  (void)hipFree(h->dls);
   for (hipEvent_t e : h->pool) (void)hipEventDestroy(e);
   delete h;
 }
 
-int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out) {
+}  // extern "C"
+
+namespace {
+
+int gru_create(int device, const dppo_gru_dims* dims, bool gauss, dppo_gru_handle** out) {
   if (!out) {
     set_error("out is NULL");
     return DPPO_EINVAL;
@@ -142,8 +188,10 @@ int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out
   dppo_gru_handle* h = new dppo_gru_handle();
   h->device = device;
   h->dims = *dims;
-  gru_layout(dims, &h->layout);
-  const int64_t* o = h->layout.offset;
+  h->gauss = gauss;
+  gru_layout(dims, &h->layout, gauss);
+  h->ls_off = h->layout.offset[0];
+  const int64_t* o = h->layout.offset + (gauss ? 1 : 0);
   h->po = GruOffsets{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11],
                      o[12], o[13]};
   h->B = (int64_t)dims->rollout_steps * dims->num_envs;
@@ -159,6 +207,8 @@ int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out
   if (e == hipSuccess) e = hipMalloc((void**)&h->slabs, (size_t)(h->G * h->slab_stride) * sizeof(float));
   if (e == hipSuccess)
     e = hipMalloc((void**)&h->sq_part, (size_t)slab_reduce_blocks(h->layout.total) * sizeof(double));
+  if (e == hipSuccess && gauss)
+    e = hipMalloc((void**)&h->dls, (size_t)(h->B * kAPad) * sizeof(float));
   if (e != hipSuccess) {
     set_error("hipMalloc (GRU workspace) failed: %s", hipGetErrorString(e));
     dppo_gru_destroy(h);
@@ -196,6 +246,18 @@ int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out
   return DPPO_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int dppo_gru_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out) {
+  return gru_create(device, dims, false, out);
+}
+
+int dppo_gru_gauss_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out) {
+  return gru_create(device, dims, true, out);
+}
+
 int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
                                 const dppo_gru_batch* batch, const int32_t* idx, int32_t m,
                                 int32_t m_total, const dppo_hparams* hp, float* grad,
@@ -210,6 +272,7 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
     set_error("dppo_gru_minibatch_grad_f32: params must be 16-byte aligned");
     return DPPO_EINVAL;
   }
+  if (gru_kind_check(h, false, "dppo_gru_minibatch_grad_f32") != DPPO_OK) return DPPO_EINVAL;
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   const dppo_gru_dims& d = h->dims;
@@ -218,6 +281,35 @@ int dppo_gru_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
                            (float)(1.0 / (double)m_total), hp->ppo_clip, hp->value_loss_weight,
                            hp->entropy_beta, h->sc, h->slabs, h->slab_stride, h->layout.total, s);
   if (rc != DPPO_OK) return rc;
+  return launch_slab_reduce(h->slabs, h->G, h->slab_stride, h->layout.total, grad, h->sq_part,
+                            LogStdTerm{-1, 0, 0.0f, 0}, s);
+}
+
+int dppo_gru_gauss_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
+                                      const dppo_gru_gauss_batch* batch, const int32_t* idx,
+                                      int32_t m, int32_t m_total, const dppo_hparams* hp,
+                                      float* grad, void* stream) {
+  if (!h || !params || !batch || !idx || !hp || !grad || m < 0 || m_total <= 0 ||
+      m > h->B || !batch->obs || !batch->actions || !batch->old_log_probs || !batch->advantages ||
+      !batch->returns || !batch->prev_dones || !batch->hx0) {
+    set_error("invalid argument to dppo_gru_gauss_minibatch_grad_f32");
+    return DPPO_EINVAL;
+  }
+  if ((uintptr_t)params % 16 != 0) {
+    set_error("dppo_gru_gauss_minibatch_grad_f32: params must be 16-byte aligned");
+    return DPPO_EINVAL;
+  }
+  if (gru_kind_check(h, true, "dppo_gru_gauss_minibatch_grad_f32") != DPPO_OK) return DPPO_EINVAL;
+  DPPO_HIP_CHECK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  const dppo_gru_dims& d = h->dims;
+  int rc = launch_gru_gauss_grad(d.gru_hidden, h->po, h->ls_off, params, *batch, idx, m, h->wmask,
+                                 h->B, d.rollout_steps, d.num_envs, d.obs_dim, d.act_dim,
+                                 (float)(1.0 / (double)m_total), hp->ppo_clip,
+                                 hp->value_loss_weight, hp->entropy_beta, h->sc, h->dls, h->slabs,
+                                 h->slab_stride, h->layout.total, s);
+  if (rc != DPPO_OK) return rc;
+  // the entropy bonus's log_std term is in the slabs already (grugrad.hip phase C)
   return launch_slab_reduce(h->slabs, h->G, h->slab_stride, h->layout.total, grad, h->sq_part,
                             LogStdTerm{-1, 0, 0.0f, 0}, s);
 }
@@ -231,11 +323,31 @@ int dppo_gru_act_f32(dppo_gru_handle* h, const float* params, const dppo_gru_ste
               "params not 16-byte aligned)");
     return DPPO_EINVAL;
   }
+  if (gru_kind_check(h, false, "dppo_gru_act_f32") != DPPO_OK) return DPPO_EINVAL;
   if (n == 0) return DPPO_OK;
   DPPO_HIP_CHECK(hipSetDevice(h->device));
   GruTimed timed(h, 0);
   return launch_gru_act(h->dims.gru_hidden, h->po, params, *step, n, h->dims.obs_dim,
                         h->dims.act_dim, seed, counter, (hipStream_t)stream);
+}
+
+int dppo_gru_gauss_act_f32(dppo_gru_handle* h, const float* params,
+                           const dppo_gru_gauss_step* step, int64_t n, uint64_t seed,
+                           uint64_t counter, void* stream) {
+  if (!h || !params || !step || n < 0 || !step->obs || !step->prev_dones || !step->hx ||
+      !step->hx_out || !step->actions || !step->log_probs || !step->values ||
+      step->hx_out == step->hx || (uintptr_t)params % 16 != 0) {
+    set_error("invalid argument to dppo_gru_gauss_act_f32 (NULL pointer, n < 0, hx_out == hx or "
+              "params not 16-byte aligned)");
+    return DPPO_EINVAL;
+  }
+  if (gru_kind_check(h, true, "dppo_gru_gauss_act_f32") != DPPO_OK) return DPPO_EINVAL;
+  if (n == 0) return DPPO_OK;
+  DPPO_HIP_CHECK(hipSetDevice(h->device));
+  GruTimed timed(h, 0);
+  return launch_gru_gauss_act(h->dims.gru_hidden, h->po, h->ls_off, params, *step, n,
+                              h->dims.obs_dim, h->dims.act_dim, seed, counter,
+                              (hipStream_t)stream);
 }
 
 int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs,
@@ -253,19 +365,10 @@ int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs
                           values, (hipStream_t)stream);
 }
 
-int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out) {
-  if (!out) {
-    set_error("out is NULL");
-    return DPPO_EINVAL;
-  }
-  const int rc = gru_validate(dims);
-  if (rc != DPPO_OK) return rc;
-  const int G = dims->gru_hidden;
-  out[0] = gru_envs(G);
-  out[1] = gru_grid(dims->num_envs, G);
-  out[2] = (int32_t)gru_lds_bytes(dims->obs_dim, G);
-  out[3] = gru_act_envs();
-  return DPPO_OK;
+int dppo_gru_plan(const dppo_gru_dims* dims, int32_t* out) { return gru_plan(dims, out, false); }
+
+int dppo_gru_gauss_plan(const dppo_gru_dims* dims, int32_t* out) {
+  return gru_plan(dims, out, true);
 }
 
 int dppo_gru_set_timing(dppo_gru_handle* h, int32_t enable) {

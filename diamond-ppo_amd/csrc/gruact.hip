@@ -23,6 +23,12 @@
 // position in the batch and on any grid.  Lanes past n clamp to env n - 1 (valid addresses) and
 // store nothing.  The Philox key, counter and per-env counter layout are the same at every width:
 // the stream does not depend on G.
+//
+// gru_act_kernel<G, OBS, true> is the Gaussian policy step (RecurrentContinuousPPO): lane k < A
+// computes mean k where it computed logit k, lane 0 draws with actdraw.h's draw_gaussian (the
+// stream dppo_act_f32 documents) and takes the log-prob from the float32 action it stores, so a
+// learn() at unchanged parameters recomputes a ratio of 1 to rounding.
+#include "actdraw.h"
 #include "grucell.h"
 #include "philox.h"
 
@@ -45,6 +51,21 @@ struct GruStepArgs {
   int64_t n;
   int D, A;
   uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
+};
+
+// The Gaussian step's arguments: `actions` points at float [n][A], `logits` at the optional
+// means, and log_std sits at ls_off of the flat layout.
+struct GruGaussStepArgs : GruStepArgs {
+  int64_t ls_off;
+};
+
+// What draw_gaussian reads (actdraw.h): no environment copy, no squash.
+struct GaussDraw {
+  int A;
+  uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
+  float* env_act;
+  int squash;
+  const float *sq_lo, *sq_half, *sq_hi;
 };
 
 // per-env LDS vectors (floats); OBS = the observation capacity, 32 or (wide_obs) 128
@@ -167,8 +188,9 @@ __device__ __forceinline__ float critic_value(const GruStepArgs& a, const EnvLds
   return P[a.po.bc2] + env_sum<G>(part);
 }
 
-template <int G, int OBS = 32>
-__global__ __launch_bounds__(kEnvsPerWg* G) void gru_act_kernel(GruStepArgs a) {
+template <int G, int OBS = 32, bool GAUSS = false>
+__global__ __launch_bounds__(kEnvsPerWg* G) void gru_act_kernel(
+    std::conditional_t<GAUSS, GruGaussStepArgs, GruStepArgs> a) {
   __shared__ __attribute__((aligned(16))) EnvLds<G, OBS> lds[kEnvsPerWg];
   const int e = threadIdx.x / G, j = threadIdx.x % G;
   const int64_t i = (int64_t)blockIdx.x * kEnvsPerWg + e;
@@ -198,6 +220,43 @@ __global__ __launch_bounds__(kEnvsPerWg* G) void gru_act_kernel(GruStepArgs a) {
     if (valid && a.logits && j < A) a.logits[i * A + j] = lg;
   }
   __syncthreads();
+  if constexpr (GAUSS) {
+    // log_std for the workgroup, zeros past A (draw_gaussian reads kAPad of them)
+    __shared__ float ls_s[kAPad];
+    if (threadIdx.x < kAPad) ls_s[threadIdx.x] = (int)threadIdx.x < A ? P[a.ls_off + threadIdx.x] : 0.0f;
+    __syncthreads();
+    if (!valid || j != 0) return;
+    float mean[kAPad], u[kAPad];
+#pragma unroll
+    for (int q = 0; q < kAPad / 4; ++q) {
+      const f32x4 x = ((const f32x4*)E.lg)[q];
+      mean[4 * q] = x[0];
+      mean[4 * q + 1] = x[1];
+      mean[4 * q + 2] = x[2];
+      mean[4 * q + 3] = x[3];
+    }
+#pragma unroll
+    for (int k = 0; k < kAPad; ++k) u[k] = 0.0f;
+    const GaussDraw dr{A, a.seed_lo, a.seed_hi, a.ctr_lo, a.ctr_hi, nullptr, 0, nullptr, nullptr,
+                       nullptr};
+    draw_gaussian<kAPad>(dr, mean, ls_s, i, u);
+    // log N(u; mean, exp(log_std)) summed over the action dims (continuous_ppo.py:41-43), from
+    // the float32 action as stored; accurate expf
+    float lp = 0.0f;
+    float* act = (float*)(void*)a.actions + i * A;
+#pragma unroll
+    for (int k = 0; k < kAPad; ++k) {
+      if (k < A) {
+        const float ls = ls_s[k];
+        const float z = (u[k] - mean[k]) * expf(-ls);
+        lp += -0.5f * z * z - ls - 0.91893853320467274178f;
+        act[k] = u[k];
+      }
+    }
+    a.log_probs[i] = lp;
+    a.values[i] = value;
+    return;
+  }
   if (!valid || j != 0) return;
 
   // Categorical(logits).sample() by inverse CDF on one uniform (as mlp.hip act_kernel), and the
@@ -267,6 +326,15 @@ int grid_for_envs(int64_t n, unsigned* grid) {
 constexpr int kWideObs = 128;  // observation capacity of the wide_obs instantiations
 
 template <int G>
+void launch_width_gauss(unsigned grid, const GruGaussStepArgs& a, hipStream_t s) {
+  const dim3 block(kEnvsPerWg * G);
+  if (a.D > 32)
+    DPPO_LAUNCH((gru_act_kernel<G, kWideObs, true>), dim3(grid), block, 0, s, a);
+  else
+    DPPO_LAUNCH((gru_act_kernel<G, 32, true>), dim3(grid), block, 0, s, a);
+}
+
+template <int G>
 void launch_width(bool act, unsigned grid, const GruStepArgs& a, hipStream_t s) {
   const dim3 block(kEnvsPerWg * G);
   if (a.D > 32) {
@@ -322,6 +390,39 @@ int gru_act_envs() { return kEnvsPerWg; }
 int launch_gru_act(int G, const GruOffsets& po, const float* params, const dppo_gru_step& st,
                    int64_t n, int D, int A, uint64_t seed, uint64_t counter, hipStream_t s) {
   return launch_step(G, true, po, params, st, n, D, A, seed, counter, s);
+}
+
+int launch_gru_gauss_act(int G, const GruOffsets& po, int64_t ls_off, const float* params,
+                         const dppo_gru_gauss_step& st, int64_t n, int D, int A, uint64_t seed,
+                         uint64_t counter, hipStream_t s) {
+  unsigned grid = 0;
+  const int rc = grid_for_envs(n, &grid);
+  if (rc != DPPO_OK) return rc;
+  GruGaussStepArgs a{};
+  a.po = po;
+  a.params = params;
+  a.obs = st.obs;
+  a.dones = st.prev_dones;
+  a.hx = st.hx;
+  a.hx_out = st.hx_out;
+  a.actions = (int32_t*)(void*)st.actions;  // float [n][A] in the Gaussian kernel
+  a.log_probs = st.log_probs;
+  a.values = st.values;
+  a.logits = st.means;
+  a.n = n;
+  a.D = D;
+  a.A = A;
+  a.seed_lo = (uint32_t)seed;
+  a.seed_hi = (uint32_t)(seed >> 32);
+  a.ctr_lo = (uint32_t)counter;
+  a.ctr_hi = (uint32_t)(counter >> 32);
+  a.ls_off = ls_off;
+  if (!dispatch_gru_width(G, [&](auto g) { launch_width_gauss<decltype(g)::value>(grid, a, s); })) {
+    set_error("no GRU rollout kernel for gru_hidden=%d", G);
+    return DPPO_EUNSUPPORTED;
+  }
+  DPPO_LAUNCH_CHECK();
+  return DPPO_OK;
 }
 
 int launch_gru_value(int G, const GruOffsets& po, const float* params, const float* obs,

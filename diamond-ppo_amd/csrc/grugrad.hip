@@ -31,6 +31,9 @@
 // gru_grad_kernel<G, true> is the form for observations of 33 to 128 floats: phase A's base layer
 // walks the observation row in blocks of 32 columns (base8_wide); everything else is the same
 // code, already written in D and D16.
+// gru_grad_kernel<G, WIDE_OBS, true> is the Gaussian head (RecurrentContinuousPPO; the loss of
+// continuous_ppo.py:276-292 on the GRU features): phase C's loss and its derivative, and one more
+// bias column in phase F (the state-independent log_std), differ; A, B, D and E are the same code.
 //
 // LDS holds the biases for the whole launch and, in one region restaged between the phases' own
 // barriers, only the weights the current phase reads: A Wb + Wih | B, D Whh | C Wa1 Wc1 Wa2 |
@@ -203,10 +206,20 @@ __device__ __forceinline__ void base8_wide(float (&z)[8], const float* bb, const
   }
 }
 
+// The Gaussian form's arguments: the categorical kernel's, then where log_std sits in the flat
+// layout and the per-sample rows [B][kAPad] of its gradient.  b.actions is float [T][N][A] here.
+struct GruGaussArgs : GruArgs {
+  int64_t ls_off;
+  float* dls;
+};
+constexpr int kGaussLds = 2 * kAPad;  // exp(-log_std) | log_std, behind the categorical image
+
 // WIDE_OBS: the form for 33 <= D <= 128 (dppo_gru_dims.wide_obs); phase A's base layer alone
-// differs.
-template <int G, bool WIDE_OBS = false>
-__global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
+// differs.  GAUSS: the Normal(mean, exp(log_std)) head; phase C's loss and phase F's log_std
+// column alone differ.
+template <int G, bool WIDE_OBS = false, bool GAUSS = false>
+__global__ __launch_bounds__(kThr) void gru_grad_kernel(
+    std::conditional_t<GAUSS, GruGaussArgs, GruArgs> a) {
   constexpr int kEnvs = kThr / G, G3 = 3 * G;
   static_assert(G3 % kGiBlk == 0 && G3 <= kThr && G % 16 == 0, "gate blocking");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -234,6 +247,14 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
   }
   if (tid < kAPad) lds[L.ba2 + tid] = tid < A ? P[po.ba2 + tid] : 0.f;
   if (tid == 0) lds[L.bc2] = P[po.bc2];
+  if constexpr (GAUSS) {
+    // 1 / sigma and log_std once per workgroup, zeros past A
+    if (tid < kAPad) {
+      const float ls = tid < A ? P[a.ls_off + tid] : 0.f;
+      lds[L.total + tid] = tid < A ? expf(-ls) : 0.f;
+      lds[L.total + kAPad + tid] = ls;
+    }
+  }
   float* Wb = W;
   float* Wih = W + kH * D;
   stage4(Wb, P + po.Wb, kH * D, tid);
@@ -428,7 +449,24 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
                  ((v1[0] * yc[4] + v1[1] * yc[5]) + (v1[2] * yc[6] + v1[3] * yc[7]));
         }
       }
-      const int act = a.b.actions[i];
+      [[maybe_unused]] int act = 0;
+      float ent = 0.f, logp = 0.f;
+      if constexpr (GAUSS) {
+        // JointNormal(mean, exp(log_std)) (continuous_ppo.py:41-47, :276-277): out[] holds the
+        // means; z_k = (a_k - mean_k) / sigma_k replaces them
+        const float* av = (const float*)a.b.actions + i * A;
+#pragma unroll
+        for (int k = 0; k < kAPad; ++k) {
+          const float ls = lds[L.total + kAPad + k];
+          const float z = k < A ? (av[k] - out[k]) * lds[L.total + k] : 0.f;
+          if (k < A) {
+            logp += -0.5f * z * z - ls - 0.91893853320467274178f;
+            ent += 1.41893853320467274178f + ls;
+          }
+          out[k] = z;
+        }
+      } else {
+      act = a.b.actions[i];
       float mx = out[0];
 #pragma unroll
       for (int k = 1; k < kAPad; ++k)
@@ -438,7 +476,6 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
       for (int k = 0; k < kAPad; ++k)
         if (k < A) se += __expf(out[k] - mx);
       const float lse = mx + __logf(se);
-      float ent = 0.f, logp = 0.f;
 #pragma unroll
       for (int k = 0; k < kAPad; ++k) {
         const float lpk = out[k] - lse;
@@ -446,6 +483,7 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
         ent -= pk * lpk;
         logp = k == act ? lpk : logp;
         out[k] = lpk;  // log-probabilities from here on
+      }
       }
       const float adv = a.b.advantages[i], ret = a.b.returns[i];
       const float ratio = __expf(logp - a.b.old_log_probs[i]);                 // ppo.py:266
@@ -460,11 +498,27 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
       s_pi += fmaxf(u, wv);
       s_v += 0.5f * (val - ret) * (val - ret);
       s_ent += ent;
+      if constexpr (GAUSS) {
+        // d logp / d mean_k = z_k / sigma_k, d logp / d log_std_k = z_k^2 - 1; the entropy's
+        // log_std derivative (1 per dimension) rides in the sample's row, so the ranks' slabs
+        // sum to the union minibatch's -ent once
+        float* dlsr = a.dls + i * kAPad;
+#pragma unroll
+        for (int k = 0; k < kAPad; ++k) {
+          const float z = out[k];
+          dl[k] = k < A ? dlogp * z * lds[L.total + k] : 0.f;
+          out[k] = k < A ? dlogp * (z * z - 1.0f) - a.ent * vm : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < kAPad / 4; ++k)
+          ((f32x4*)dlsr)[k] = (f32x4){out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]};
+      } else {
 #pragma unroll
       for (int k = 0; k < kAPad; ++k) {
         const float pk = k < A ? __expf(out[k]) : 0.f;
         dl[k] = k < A ? dlogp * ((k == act ? 1.f : 0.f) - pk) + a.ent * vm * pk * (out[k] + ent)
                       : 0.f;
+      }
       }
       // head backward: dya = (Wa2^T dl)(1 - ya^2), dyc = Wc2 dv (1 - yc^2),
       // dh' = Wa1^T dya + Wc1^T dyc
@@ -508,6 +562,10 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
       }
 #pragma unroll
       for (int k = 0; k < G / 4; ++k) dhor[k] = zero;
+      if constexpr (GAUSS) {
+#pragma unroll
+        for (int k = 0; k < kAPad / 4; ++k) ((f32x4*)(a.dls + i * kAPad))[k] = zero;
+      }
     }
 #pragma unroll
     for (int k = 0; k < kAPad / 4; ++k)
@@ -605,8 +663,8 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
     }
   }
   {
-    // bias columns: bb 64 | bih 3G | bhh 3G | ba1 64 | bc1 64 | ba2 A | bc2 1
-    const int nb = kH + G3 + G3 + kH + kH + A + 1;
+    // bias columns: bb 64 | bih 3G | bhh 3G | ba1 64 | bc1 64 | ba2 A | bc2 1 | (GAUSS) log_std A
+    const int nb = kH + G3 + G3 + kH + kH + A + 1 + (GAUSS ? A : 0);
     for (int c = tid; c < nb; c += kThr) {
       const float* src;
       int ld, col;
@@ -618,7 +676,12 @@ __global__ __launch_bounds__(kThr) void gru_grad_kernel(GruArgs a) {
       else if ((k -= G3) < kH) { src = sc.dya; ld = kH; col = k; off = po.ba1 + k; }
       else if ((k -= kH) < kH) { src = sc.dyc; ld = kH; col = k; off = po.bc1 + k; }
       else if ((k -= kH) < A) { src = sc.dl; ld = kAPad; col = k; off = po.ba2 + k; }
-      else { src = sc.dv; ld = kAPad; col = 0; off = po.bc2; }
+      else {
+        src = sc.dv; ld = kAPad; col = 0; off = po.bc2;
+        if constexpr (GAUSS) {
+          if ((k -= A) > 0) { src = a.dls; col = k - 1; off = a.ls_off + k - 1; }
+        }
+      }
       // sample order s = 0, 1, ...; the loads of kSumAhead samples in flight together
       float sum = 0.f;
       int s = 0;
@@ -674,6 +737,24 @@ int launch_g(const GruArgs& a, hipStream_t s) {
   return DPPO_OK;
 }
 
+template <int G>
+int launch_g_gauss(const GruGaussArgs& a, hipStream_t s) {
+  static const bool attr = [] {
+    raise_dyn_lds((const void*)gru_grad_kernel<G, false, true>);
+    raise_dyn_lds((const void*)gru_grad_kernel<G, true, true>);
+    return true;
+  }();
+  (void)attr;
+  const dim3 grid(gru_grid(a.N, G));
+  const size_t lds = gru_gauss_lds_bytes(a.D, G);
+  if (a.D > 32)
+    DPPO_LAUNCH((gru_grad_kernel<G, true, true>), grid, dim3(kThr), lds, s, a);
+  else
+    DPPO_LAUNCH((gru_grad_kernel<G, false, true>), grid, dim3(kThr), lds, s, a);
+  DPPO_LAUNCH_CHECK();
+  return DPPO_OK;
+}
+
 }  // namespace
 
 int gru_envs(int G) { return kThr / G; }
@@ -682,10 +763,13 @@ int gru_grid(int N, int G) { return (N + gru_envs(G) - 1) / gru_envs(G); }
 
 size_t gru_lds_bytes(int D, int G) { return (size_t)gru_lds(D, G).total * sizeof(float); }
 
-int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
-                    const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
-                    int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
-                    float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s) {
+size_t gru_gauss_lds_bytes(int D, int G) {
+  return (size_t)(gru_lds(D, G).total + kGaussLds) * sizeof(float);
+}
+
+namespace {
+
+int build_mask(const int32_t* idx, int32_t m, float* wmask, int64_t B, hipStream_t s) {
   DPPO_HIP_CHECK(hipMemsetAsync(wmask, 0, (size_t)B * sizeof(float), s));
   if (m > 0) {
     int g = (m + 255) / 256;
@@ -693,6 +777,53 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
     DPPO_LAUNCH(mask_kernel, dim3(g), dim3(256), 0, s, idx, m, wmask);
     DPPO_LAUNCH_CHECK();
   }
+  return DPPO_OK;
+}
+
+}  // namespace
+
+int launch_gru_gauss_grad(int G, const GruOffsets& po, int64_t ls_off, const float* params,
+                          const dppo_gru_gauss_batch& b, const int32_t* idx, int32_t m,
+                          float* wmask, int64_t B, int T, int N, int D, int A, float inv_m,
+                          float clip_eps, float vf, float ent, const GruScratch& sc, float* dls,
+                          float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s) {
+  int rc = build_mask(idx, m, wmask, B, s);
+  if (rc != DPPO_OK) return rc;
+  GruGaussArgs a{};
+  a.po = po;
+  a.params = params;
+  // the two batch structs differ in the element type behind `actions` alone
+  a.b = dppo_gru_batch{b.obs, (const int32_t*)(const void*)b.actions, b.old_log_probs,
+                       b.advantages, b.returns, b.prev_dones, b.hx0};
+  a.wmask = wmask;
+  a.T = T;
+  a.N = N;
+  a.D = D;
+  a.D16 = (D + 15) / 16 * 16;
+  a.A = A;
+  a.inv_m = inv_m;
+  a.clip_eps = clip_eps;
+  a.vf = vf;
+  a.ent = ent;
+  a.sc = sc;
+  a.slabs = slabs;
+  a.slab_stride = slab_stride;
+  a.p_total = p_total;
+  a.ls_off = ls_off;
+  a.dls = dls;
+  if (!dispatch_gru_width(G, [&](auto g) { rc = launch_g_gauss<decltype(g)::value>(a, s); })) {
+    set_error("no GRU gradient kernel for gru_hidden=%d", G);
+    return DPPO_EUNSUPPORTED;
+  }
+  return rc;
+}
+
+int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo_gru_batch& b,
+                    const int32_t* idx, int32_t m, float* wmask, int64_t B, int T, int N, int D,
+                    int A, float inv_m, float clip_eps, float vf, float ent, const GruScratch& sc,
+                    float* slabs, int64_t slab_stride, int64_t p_total, hipStream_t s) {
+  int rc = build_mask(idx, m, wmask, B, s);
+  if (rc != DPPO_OK) return rc;
   GruArgs a{};
   a.po = po;
   a.params = params;
@@ -711,7 +842,6 @@ int launch_gru_grad(int G, const GruOffsets& po, const float* params, const dppo
   a.slabs = slabs;
   a.slab_stride = slab_stride;
   a.p_total = p_total;
-  int rc = DPPO_OK;
   if (!dispatch_gru_width(G, [&](auto g) { rc = launch_g<decltype(g)::value>(a, s); })) {
     set_error("no GRU gradient kernel for gru_hidden=%d", G);
     return DPPO_EUNSUPPORTED;

@@ -41,6 +41,8 @@ EXPORTED = [
     "dppo_gru_plan",
     "dppo_ppo_loss_f32", "dppo_policy_logp_f32", "dppo_ppo_loss_plan",
     "dppo_gru_scan_plan", "dppo_gru_scan_fwd_f32", "dppo_gru_scan_bwd_f32",
+    "dppo_gru_gauss_param_layout", "dppo_gru_gauss_plan", "dppo_gru_gauss_create",
+    "dppo_gru_gauss_minibatch_grad_f32", "dppo_gru_gauss_act_f32",
 ]
 TIMING_CLASSES = ["eval", "gae", "adv_stats", "pack", "grad", "slab_reduce", "clip_adam",
                   "allreduce", "perm", "reduce_adam", "gae_probe"]
@@ -94,6 +96,18 @@ class GruStep(ctypes.Structure):
                 ("hx", ctypes.c_void_p), ("hx_out", ctypes.c_void_p),
                 ("actions", ctypes.c_void_p), ("log_probs", ctypes.c_void_p),
                 ("values", ctypes.c_void_p), ("logits", ctypes.c_void_p)]
+
+
+class GruGaussBatch(GruBatch):
+    """dppo_gru_gauss_batch: dppo_gru_batch's fields, ``actions`` float32 [T][N][A]."""
+
+
+class GruGaussStep(ctypes.Structure):
+    """dppo_gru_gauss_step: device pointers of one Gaussian rollout step (means optional)."""
+    _fields_ = [("obs", ctypes.c_void_p), ("prev_dones", ctypes.c_void_p),
+                ("hx", ctypes.c_void_p), ("hx_out", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("log_probs", ctypes.c_void_p),
+                ("values", ctypes.c_void_p), ("means", ctypes.c_void_p)]
 
 
 class Rollout(ctypes.Structure):
@@ -212,6 +226,13 @@ def load():
         "dppo_gru_scan_plan": (ctypes.c_int, [i32, i64, i64, P(i64)]),
         "dppo_gru_scan_fwd_f32": (ctypes.c_int, [vp] * 7 + [i64, i64, i32, vp]),
         "dppo_gru_scan_bwd_f32": (ctypes.c_int, [vp] * 10 + [i64, i64, i32, vp]),
+        "dppo_gru_gauss_param_layout": (ctypes.c_int, [P(GruDims), P(Layout)]),
+        "dppo_gru_gauss_plan": (ctypes.c_int, [P(GruDims), vp]),
+        "dppo_gru_gauss_create": (ctypes.c_int, [ctypes.c_int, P(GruDims), P(vp)]),
+        "dppo_gru_gauss_minibatch_grad_f32": (ctypes.c_int, [vp, vp, P(GruGaussBatch), vp, i32,
+                                                             i32, P(HParams), vp, vp]),
+        "dppo_gru_gauss_act_f32": (ctypes.c_int, [vp, vp, P(GruGaussStep), i64, ctypes.c_uint64,
+                                                  ctypes.c_uint64, vp]),
         "dppo_set_timing": (ctypes.c_int, [vp, i32]),
         "dppo_get_timing": (ctypes.c_int, [vp, vp, vp]),
     }
@@ -524,16 +545,20 @@ class GruHandle:
     """Owns one dppo_gru_handle (RecurrentPPO's fused minibatch-gradient workspace; the
     rollout kernels dppo_gru_act_f32 / dppo_gru_value_f32 take it for its shape and layout)."""
 
-    def __init__(self, device_index: int, dims: GruDims):
+    def __init__(self, device_index: int, dims: GruDims, gauss: bool = False):
+        """``gauss``: the Gaussian head (dppo_gru_gauss_create and its 15-tensor layout)."""
         self.lib = load()
         self.dims = dims
+        self.gauss = bool(gauss)
+        kind = "dppo_gru_gauss_" if self.gauss else "dppo_gru_"
         h = ctypes.c_void_p()
-        check(self.lib.dppo_gru_create(int(device_index), ctypes.byref(dims), ctypes.byref(h)),
-              "dppo_gru_create")
+        check(getattr(self.lib, kind + "create")(int(device_index), ctypes.byref(dims),
+                                                 ctypes.byref(h)), kind + "create")
         self.h = h
         self.layout = Layout()
-        check(self.lib.dppo_gru_param_layout(ctypes.byref(dims), ctypes.byref(self.layout)),
-              "dppo_gru_param_layout")
+        check(getattr(self.lib, kind + "param_layout")(ctypes.byref(dims),
+                                                       ctypes.byref(self.layout)),
+              kind + "param_layout")
 
     def set_timing(self, enable: bool):
         check(self.lib.dppo_gru_set_timing(self.h, int(bool(enable))), "dppo_gru_set_timing")

@@ -267,6 +267,12 @@ class RecurrentPPO:
     # autograd.  Where fused_gru / fused_rollout serve the agent they win as before.  Off by
     # default: the bits then differ from nn.GRU's
     fused_core = False
+    # the head, for the subclass with the Gaussian one (RecurrentContinuousPPO): which loss the
+    # torch loop evaluates, and the fused minibatch launch with its batch struct and action type
+    continuous = False
+    _grad_entry = "dppo_gru_minibatch_grad_f32"
+    _batch_struct = N.GruBatch
+    _action_dtype = torch.int32
 
     def __init__(self, env_fn: Callable[[], Any], cfg: RecurrentPPOConfig = RecurrentPPOConfig(),
                  network_cls: Any = RecurrentActorCriticNetwork, envs=None) -> None:
@@ -330,6 +336,12 @@ class RecurrentPPO:
             if isinstance(m, GRUCore):
                 m.fused_scan = on
         return on
+
+    def _policy_terms(self, observations, hx, prev_dones):
+        """(actor output [T, N, A], log_std or None, values [T, N]) over the whole rollout, under
+        autograd: what the torch learn loop differentiates."""
+        nl, nv, _ = self.network.get_logits_values_and_hx(observations, hx, prev_dones)
+        return nl, None, nv
 
     def rollout(self):
         """recurrent_ppo.py:205-263 with tensor-safe hidden-state handling."""
@@ -499,29 +511,31 @@ class RecurrentPPO:
         record = [] if self._set_core_scan() else None
         scans0 = CORE_SCAN_CALLS[0]
         if fused_loss:
-            act32 = actions.to(torch.int32).contiguous()
+            act32 = actions.to(self._action_dtype).contiguous()
             old_lp, adv_c, ret_c = (x.float().contiguous() for x in
                                     (log_probs, advantages, returns))
         for b_idx in idx:
             for mb_idx in b_idx:
                 self.flat.grad.zero_()
-                nl, nv, _ = self.network.get_logits_values_and_hx(observations, hx, prev_dones)
+                nl, ls, nv = self._policy_terms(observations, hx, prev_dones)
                 nl, nv = flatten(nl)[mb_idx], flatten(nv)[mb_idx]
+                if ls is not None:
+                    ls = flatten(ls)[mb_idx]
                 if fused_loss:
                     calls0 = LOSS_KERNEL_CALLS[0]
                     loss, terms = fused_ppo_loss(
-                        nl, nv, None, actions=act32, old_log_probs=old_lp, advantages=adv_c,
+                        nl, nv, ls, actions=act32, old_log_probs=old_lp, advantages=adv_c,
                         returns=ret_c, idx=mb_idx, clip=cfg.ppo_clip,
                         value_loss_weight=cfg.value_loss_weight, entropy_beta=cfg.entropy_beta,
-                        scale=1.0 / world if world > 1 else 1.0, continuous=False)
+                        scale=1.0 / world if world > 1 else 1.0, continuous=self.continuous)
                     self.loss_head_calls += LOSS_KERNEL_CALLS[0] - calls0
                     if record is not None:
                         record.append(terms[:4].clone())
                 else:
                     loss, l_pi, l_v, ent, _ = torch_ppo_terms(
-                        nl, nv, None, actions[mb_idx], log_probs[mb_idx], advantages[mb_idx],
+                        nl, nv, ls, actions[mb_idx], log_probs[mb_idx], advantages[mb_idx],
                         returns[mb_idx], cfg.ppo_clip, cfg.value_loss_weight, cfg.entropy_beta,
-                        False)
+                        self.continuous)
                     if record is not None:
                         record.append(torch.stack([loss, l_pi, l_v, ent]).detach())
                     if world > 1:
@@ -547,12 +561,14 @@ class RecurrentPPO:
         cfg, lib = self.cfg, self.gru.lib
         f32 = lambda x: x.to(torch.float32).contiguous()
         obs = f32(observations)
-        act = actions.to(torch.int32).contiguous()
+        act = actions.to(self._action_dtype).contiguous()
         old_lp, adv, ret = f32(log_probs), f32(advantages), f32(returns)
         dones = prev_dones.to(torch.uint8).contiguous()
         hx0 = f32(hx.reshape(cfg.num_envs, cfg.gru_hidden_dim))
-        batch = N.GruBatch(obs.data_ptr(), act.data_ptr(), old_lp.data_ptr(), adv.data_ptr(),
-                           ret.data_ptr(), dones.data_ptr(), hx0.data_ptr())
+        batch = self._batch_struct(obs.data_ptr(), act.data_ptr(), old_lp.data_ptr(),
+                                   adv.data_ptr(),
+                                   ret.data_ptr(), dones.data_ptr(), hx0.data_ptr())
+        grad_fn = getattr(lib, self._grad_entry)
         hp = hparams(cfg, lr, step)
         idx32 = idx.to(torch.int32).contiguous()
         mb = idx32.shape[-1]
@@ -562,10 +578,10 @@ class RecurrentPPO:
         for e in range(idx32.shape[0]):
             for j in range(idx32.shape[1]):
                 mb_idx = idx32[e, j]
-                N.check(lib.dppo_gru_minibatch_grad_f32(
+                N.check(grad_fn(
                     self.gru.h, self.flat.flat.data_ptr(), ctypes.byref(batch), mb_idx.data_ptr(),
                     mb, m_total, ctypes.byref(hp), self.flat.grad.data_ptr(), stream),
-                    "dppo_gru_minibatch_grad_f32")
+                    self._grad_entry)
                 if world > 1:
                     torch.distributed.all_reduce(self.flat.grad)
                 losses.append(self.flat.grad[total:total + 3].clone())

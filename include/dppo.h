@@ -531,6 +531,65 @@ int dppo_gru_value_f32(dppo_gru_handle* h, const float* params, const float* obs
 int dppo_gru_set_timing(dppo_gru_handle* h, int32_t enable);
 int dppo_gru_get_timing(dppo_gru_handle* h, double* ms_sum, int64_t* counts);
 
+/* ---- RecurrentContinuousPPO: the same GRU network with a Gaussian head (no reference
+ * counterpart: the reference has no recurrent Gaussian agent; the head restates
+ * continuous_ppo.py:40-47, :50-111 and the loss :276-292 on the GRU features of
+ * recurrent_ppo.py:94-149).  Same handle type, dims (act_dim = action dimensions A <= 16),
+ * validation and workspace as above; the handle remembers its kind.  dppo_gru_destroy,
+ * dppo_gru_value_f32 and the timing calls serve both kinds; a Gaussian handle passed to
+ * dppo_gru_minibatch_grad_f32 / dppo_gru_act_f32, or a categorical one to the two gauss launches,
+ * returns DPPO_EINVAL without a launch. */
+
+/* Flat parameter layout of RecurrentContinuousActorCriticNetwork (named_parameters() order,
+ * 16-float aligned offsets; 15 tensors, tensor 0 = actor_log_std [1][A], continuous_ppo.py:95). */
+int dppo_gru_gauss_param_layout(const dppo_gru_dims* dims, dppo_layout* out);
+/* As dppo_gru_plan; out[2] counts the Gaussian form's 128 further bytes of LDS. */
+int dppo_gru_gauss_plan(const dppo_gru_dims* dims, int32_t* out);
+/* As dppo_gru_create. */
+int dppo_gru_gauss_create(int device, const dppo_gru_dims* dims, dppo_gru_handle** out);
+
+/* dppo_gru_batch with the Gaussian samples as actions. */
+typedef struct dppo_gru_gauss_batch {
+  const float* obs;           /* [T][N][D] */
+  const float* actions;       /* [T][N][A] */
+  const float* old_log_probs; /* [T][N] */
+  const float* advantages;    /* [T][N] */
+  const float* returns;       /* [T][N] */
+  const uint8_t* prev_dones;  /* [T][N] */
+  const float* hx0;           /* [N][gru_hidden] */
+} dppo_gru_gauss_batch;
+
+/* dppo_gru_minibatch_grad_f32's contract with the JointNormal(mean, exp(actor_log_std)) loss
+ * (continuous_ppo.py:276-292): log-prob and entropy summed over the action dims, the entropy
+ * bonus's actor_log_std gradient (-entropy_beta per dimension over the whole minibatch) included
+ * sample by sample with weight 1 / m_total, so the ranks' gradients sum to the union
+ * minibatch's.  grad [layout.total + 8], the loss sums {policy, value, entropy} after the
+ * gradient.  Stream-ordered, deterministic, params 16-byte aligned. */
+int dppo_gru_gauss_minibatch_grad_f32(dppo_gru_handle* h, const float* params,
+                                      const dppo_gru_gauss_batch* batch, const int32_t* idx,
+                                      int32_t m, int32_t m_total, const dppo_hparams* hp,
+                                      float* grad, void* stream);
+
+/* One rollout step of n envs, device pointers. */
+typedef struct dppo_gru_gauss_step {
+  const float* obs;          /* [n][D] */
+  const uint8_t* prev_dones; /* [n] */
+  const float* hx;           /* [n][G] */
+  float* hx_out;             /* [n][G]; must not alias hx */
+  float* actions;            /* [n][A] Gaussian sample */
+  float* log_probs;          /* [n] joint log-prob of the sample */
+  float* values;             /* [n] */
+  float* means;              /* optional [n][A], may be NULL */
+} dppo_gru_gauss_step;
+
+/* dppo_gru_act_f32's contract with a Normal(mean, exp(actor_log_std)) draw
+ * (continuous_ppo.py:100-105): Box-Muller on Philox4x32-10, the stream dppo_act_f32 documents
+ * (counter = (sample index, block of four action dims << 24 in the high sample word, `counter`)),
+ * and the log-prob evaluated from the float32 action as stored and the mean (accurate expf). */
+int dppo_gru_gauss_act_f32(dppo_gru_handle* h, const float* params,
+                           const dppo_gru_gauss_step* step, int64_t n, uint64_t seed,
+                           uint64_t counter, void* stream);
+
 /* ---- PPO loss head for a network that runs under the caller's autograd (custom network_cls,
  * shapes outside the fused classes).  Handle-less, stream-ordered, allocates nothing, no host
  * synchronisation, no floating-point atomics: the same inputs give the same bits. */

@@ -23,6 +23,14 @@ slowest learn is below the other's fastest:
 
     python tools/bench_recurrent_learn.py --obs-dim 128 --act-dim 6 --wide-observations \
         --sizes 32 8192 --out bench_out/recurrent_wide_obs_learn.json
+
+`--continuous` times RecurrentContinuousPPO (the Gaussian head; `--act-dim` = action dimensions)
+the same way: `fused` (gru_grad_kernel<G, WIDE_OBS, true>), `torch` (fused_gru off) and
+`torch_core` (that with `fused_core`) share the weights and alternate; the rollout's actions are
+drawn from the agent's own policy and carry its log-probs:
+
+    python tools/bench_recurrent_learn.py --continuous --obs-dim 17 --act-dim 6 \
+        --sizes 32 8192 --out profiles/recurrent_gauss_learn.json
 """
 import argparse
 import json
@@ -47,11 +55,21 @@ SIZES = [32, 1024, 8192]
 WIDTHS = [16, 32, 64]
 
 
-def make_agent(Nn, G, fused, D=D, A=A, wide_obs=False, core=False):
+def make_agent(Nn, G, fused, D=D, A=A, wide_obs=False, core=False, continuous=False):
     """fused: the minibatch kernel (with wide_obs: asked for through the config flag).  Not fused:
     the torch loop, by fused_gru = False or, where wide_obs is tested, by leaving the flag off."""
     np.random.seed(0)
     torch.manual_seed(0)
+    if continuous:
+        envs = gym_stub.SyncVectorEnv(
+            [lambda: gym_stub.SyntheticEnv(D, continuous=True, act_dim=A)] * Nn)
+        cfg = diamond.RecurrentContinuousPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
+                                                   gru_hidden_dim=G, wide_observations=wide_obs)
+        agent = diamond.RecurrentContinuousPPO(None, cfg, envs=envs)
+        assert agent.gru is not None
+        agent.fused_gru = fused
+        agent.fused_core = core
+        return agent
     envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
     cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
                                      gru_hidden_dim=G, wide_observations=wide_obs and fused)
@@ -73,6 +91,18 @@ def experience(Nn, G, device, seed=0, D=D, A=A):
              g(rng.standard_normal(Nn)), g(rng.standard_normal(Nn)), hx] for _ in range(T)]
 
 
+def gaussian_experience(agent, exp):
+    """`exp` with float32 actions [N, A] drawn from the agent's own policy and their log-probs."""
+    from diamond.continuous_ppo import JointNormal
+    with torch.no_grad():
+        mean, ls, _, _ = agent.network.get_means_log_stds_values_and_hx(
+            torch.stack([r[0] for r in exp]), exp[0][9], torch.stack([r[5] for r in exp]))
+        dist = JointNormal(mean, ls.exp())
+        act = dist.sample()
+        lp = dist.log_prob(act)
+    return [[r[0], act[t], *r[2:6], lp[t], *r[7:]] for t, r in enumerate(exp)]
+
+
 def timed_learn(agent, exp):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -81,12 +111,16 @@ def timed_learn(agent, exp):
     return (time.perf_counter() - t0) * 1e3
 
 
-def run(Nn, G, warmup, learns, D=D, A=A, wide_obs=False):
-    agents = {"fused": make_agent(Nn, G, True, D, A, wide_obs),
-              "torch": make_agent(Nn, G, False, D, A, wide_obs)}
-    if wide_obs:
-        agents["torch_core"] = make_agent(Nn, G, False, D, A, wide_obs, core=True)
+def run(Nn, G, warmup, learns, D=D, A=A, wide_obs=False, continuous=False):
+    agents = {"fused": make_agent(Nn, G, True, D, A, wide_obs, continuous=continuous),
+              "torch": make_agent(Nn, G, False, D, A, wide_obs, continuous=continuous)}
+    three = wide_obs or continuous
+    if three:
+        agents["torch_core"] = make_agent(Nn, G, False, D, A, wide_obs, core=True,
+                                          continuous=continuous)
     exp = experience(Nn, G, agents["fused"].device, D=D, A=A)
+    if continuous:
+        exp = gaussian_experience(agents["fused"], exp)
     ms = {k: [] for k in agents}
     for r in range(warmup + learns):
         for k, agent in agents.items():
@@ -103,8 +137,11 @@ def run(Nn, G, warmup, learns, D=D, A=A, wide_obs=False):
     out["fused_is_slower"] = out["torch_over_fused"] < 1.0
     inside = lambda a, b: out[b + "_ms_min"] <= out[a + "_ms_median"] <= out[b + "_ms_max"]
     out["medians_inside_each_others_spread"] = inside("fused", "torch") and inside("torch", "fused")
+    if continuous:
+        out["continuous"] = True
     if wide_obs:
         out["wide_observations"] = True
+    if three:
         out["torch_core_over_fused"] = out["torch_core_ms_median"] / out["fused_ms_median"]
         for k in ("torch", "torch_core"):
             out[f"fused_max_below_{k}_min"] = out["fused_ms_max"] < out[k + "_ms_min"]
@@ -121,11 +158,13 @@ def main():
     ap.add_argument("--obs-dim", type=int, default=D)
     ap.add_argument("--act-dim", type=int, default=A)
     ap.add_argument("--wide-observations", action="store_true")
+    ap.add_argument("--continuous", action="store_true")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "rows": []}
     for G in a.gru_hidden:
         for Nn in a.sizes:
-            r = run(Nn, G, a.warmup, a.learns, a.obs_dim, a.act_dim, a.wide_observations)
+            r = run(Nn, G, a.warmup, a.learns, a.obs_dim, a.act_dim, a.wide_observations,
+                    a.continuous)
             print(json.dumps(r), flush=True)
             res["rows"].append(r)
     if a.out:

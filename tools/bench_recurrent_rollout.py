@@ -26,6 +26,9 @@ the other's fastest:
 
     python tools/bench_recurrent_rollout.py --gru-hidden 16 32 64 --obs-dim 128 --act-dim 6 \
         --wide-observations --sizes 32 8192 --out bench_out/recurrent_wide_obs_rollout.json
+
+`--continuous` times RecurrentContinuousPPO (the Gaussian head; `--act-dim` = action dimensions):
+`fused` (dppo_gru_gauss_act_f32 + dppo_gru_value_f32), `torch` and `torch_core` alternate.
 """
 import argparse
 import json
@@ -49,16 +52,24 @@ T, D, A = 32, 8, 4      # D, A: the defaults of --obs-dim / --act-dim
 SIZES = [32, 1024, 8192]
 
 
-def make_agent(Nn, fused, G=16, D=D, A=A, wide_obs=False, core=False):
+def make_agent(Nn, fused, G=16, D=D, A=A, wide_obs=False, core=False, continuous=False):
     """fused: the step kernels (with wide_obs: asked for through the config flag).  Not fused:
     the torch rollout; where wide_obs is tested the flag stays off, so no fused path exists."""
     np.random.seed(0)
     torch.manual_seed(0)
-    envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
-    cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
-                                     gru_hidden_dim=G, wide_observations=wide_obs and fused)
-    agent = diamond.RecurrentPPO(None, cfg, envs=envs)
-    assert (agent.gru is not None) == (fused or not wide_obs)
+    if continuous:
+        envs = gym_stub.SyncVectorEnv(
+            [lambda: gym_stub.SyntheticEnv(D, continuous=True, act_dim=A)] * Nn)
+        cfg = diamond.RecurrentContinuousPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
+                                                   gru_hidden_dim=G, wide_observations=wide_obs)
+        agent = diamond.RecurrentContinuousPPO(None, cfg, envs=envs)
+        assert agent.gru is not None
+    else:
+        envs = gym_stub.SyncVectorEnv([lambda: gym_stub.SyntheticEnv(D, A)] * Nn)
+        cfg = diamond.RecurrentPPOConfig(rollout_steps=T, num_envs=Nn, verbose=False,
+                                         gru_hidden_dim=G, wide_observations=wide_obs and fused)
+        agent = diamond.RecurrentPPO(None, cfg, envs=envs)
+        assert (agent.gru is not None) == (fused or not wide_obs)
     agent.fused_rollout = fused
     agent.fused_core = core
     agent.current_observations, _ = agent.envs.reset(seed=1)
@@ -75,11 +86,13 @@ def timed_rollout(agent):
     return (time.perf_counter() - t0) * 1e3
 
 
-def run(Nn, warmup, rollouts, kernel_rollouts, G=16, D=D, A=A, wide_obs=False):
-    agents = {"fused": make_agent(Nn, True, G, D, A, wide_obs),
-              "torch": make_agent(Nn, False, G, D, A, wide_obs)}
-    if wide_obs:
-        agents["torch_core"] = make_agent(Nn, False, G, D, A, wide_obs, core=True)
+def run(Nn, warmup, rollouts, kernel_rollouts, G=16, D=D, A=A, wide_obs=False, continuous=False):
+    agents = {"fused": make_agent(Nn, True, G, D, A, wide_obs, continuous=continuous),
+              "torch": make_agent(Nn, False, G, D, A, wide_obs, continuous=continuous)}
+    three = wide_obs or continuous
+    if three:
+        agents["torch_core"] = make_agent(Nn, False, G, D, A, wide_obs, core=True,
+                                          continuous=continuous)
     ms = {k: [] for k in agents}
     for r in range(warmup + rollouts):
         for k, agent in agents.items():
@@ -94,8 +107,11 @@ def run(Nn, warmup, rollouts, kernel_rollouts, G=16, D=D, A=A, wide_obs=False):
         out[k + "_ms_min"], out[k + "_ms_max"] = min(v), max(v)
     out["torch_over_fused"] = out["torch_ms_median"] / out["fused_ms_median"]
     out["fused_is_slower"] = out["torch_over_fused"] < 1.0
+    if continuous:
+        out["continuous"] = True
     if wide_obs:
         out["wide_observations"] = True
+    if three:
         out["torch_core_over_fused"] = out["torch_core_ms_median"] / out["fused_ms_median"]
         for k in ("torch", "torch_core"):
             out[f"fused_max_below_{k}_min"] = out["fused_ms_max"] < out[k + "_ms_min"]
@@ -122,12 +138,13 @@ def main():
     ap.add_argument("--obs-dim", type=int, default=D)
     ap.add_argument("--act-dim", type=int, default=A)
     ap.add_argument("--wide-observations", action="store_true")
+    ap.add_argument("--continuous", action="store_true")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "env": "tests/golden/gym_stub.py", "sizes": []}
     for G in a.gru_hidden:
         for Nn in a.sizes:
             r = run(Nn, a.warmup, a.rollouts, a.kernel_rollouts, G, a.obs_dim, a.act_dim,
-                    a.wide_observations)
+                    a.wide_observations, a.continuous)
             print(json.dumps(r), flush=True)
             res["sizes"].append(r)
     if a.out:
